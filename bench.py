@@ -21,6 +21,13 @@ configs, one command each (defaults follow the reference chapter configs,
     bench.py --parallelism tp                             # ch 6 (TP=N)
     bench.py --parallelism 2d  --tensor-parallel 2        # ch 7 (70B at N>=4)
 
+A plain run sets up, warms up, times --steps steps and prints the result
+line; it does nothing else.  --full is where any extra measurement (other
+configs, baselines, per-kernel figures) belongs — there is none today, so
+--full runs exactly the plain benchmark.  --dump-outputs DIR writes what
+the last timed step computed (see dump_outputs) for build-to-build
+comparison; inputs and initial weights are seeded, identical run to run.
+
 Rank 0 prints exactly one JSON line: whole-job tokens/s (aggregate over all
 N GPUs), ms_per_step = MAX over ranks, peak HBM, config.  vs_baseline is
 null: the reference's only numeric figure (~137 tok/s/GPU) is its
@@ -80,7 +87,18 @@ def parse_args():
                         "fused AdamW avoids the un-overlapped post-step "
                         "shard all-gather)")
     p.add_argument("--device", default=None)
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed (its loss, and a fixed seeded sample "
+                        "of the parameters it updated) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every extra measurement beyond the "
+                        "headline figure (none exist today: same as a "
+                        "plain run)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
 
 
 def _maybe_load_tunableop(model_name: str, device):
@@ -101,6 +119,35 @@ def _maybe_load_tunableop(model_name: str, device):
         tunable.read_file(str(f))
     except Exception as e:  # noqa: BLE001 - perf feature, never fatal
         print(f"tunableop load failed: {e}", file=sys.stderr)
+
+
+# --dump-outputs: elements sampled per parameter tensor (fp32; ~3 MB for
+# the 8B model, so the whole dump stays far under 64 MB)
+_DUMP_SAMPLE = 4096
+
+
+def dump_outputs(out_dir, loss, model):
+    """Write the results of the last timed step as float32 .npy files:
+    loss.npy (the value step() returned) and params_sample.npy (the
+    training state it left behind: up to _DUMP_SAMPLE elements of every
+    parameter of this rank, at fixed seeded positions, concatenated in
+    named_parameters() order).  Same arguments -> same positions."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "loss.npy",
+            loss.detach().float().cpu().numpy().reshape(1))
+    gen = torch.Generator().manual_seed(4321)
+    parts = []
+    for _, p in model.named_parameters():
+        flat = p.detach().flatten()
+        n = flat.numel()
+        if n > _DUMP_SAMPLE:
+            idx = torch.randint(n, (_DUMP_SAMPLE,), generator=gen)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(out_dir / "params_sample.npy", torch.cat(parts).numpy())
 
 
 def build(par, args, config, device, world):
@@ -290,7 +337,7 @@ def main():
     sync()          # RCCL barrier enqueues device work; drain it too
     t0 = time.time()
     for _ in range(args.steps):
-        step()
+        last_loss = step().detach()
     barrier()
     sync()
     t1 = time.time()
@@ -305,6 +352,9 @@ def main():
     tokens_per_s = dp_size * B * S / (ms_per_step / 1000.0)
     peak_gb = (torch.cuda.max_memory_allocated(device) / 1e9
                if device.type == "cuda" else 0.0)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_loss, model)
 
     if rank == 0:
         print(json.dumps({

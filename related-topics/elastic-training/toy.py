@@ -59,7 +59,8 @@ def main():
                 raise
             try:
                 dist.destroy_process_group()
-            except (RuntimeError, ValueError):
+            except (RuntimeError, ValueError, AssertionError):
+                # a failed init leaves no default group to destroy
                 pass
             print(f"[rank={rank}] init race (attempt {attempt}); retrying")
             time.sleep(1.0 + 0.5 * rank)

@@ -45,6 +45,50 @@ def test_bench_single_process(par):
     assert rec["config"]["global_batch"] == 2
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32
+    .npy, reproducibly (seeded inputs and weights: two runs with the same
+    arguments agree); --full keeps the plain contract and the plain
+    figure's meaning; --steps sets the number of timed steps."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, str(REPO / "bench.py"), "--gpus", "1",
+             "--dump-outputs", str(d)] + COMMON + extra,
+            capture_output=True, text=True, timeout=300, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        rec = _check_contract(lines[0], 1)
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert rec["unit"] == "tokens/s" and rec["higher_is_better"] is True
+        # value is tokens per second of one timed step
+        assert rec["value"] == pytest.approx(
+            2 * 64 / (rec["ms_per_step"] / 1000.0))
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["loss.npy", "params_sample.npy"]
+        arrs = {f: np.load(d / f) for f in files}
+        for a in arrs.values():
+            assert a.dtype == np.float32 and a.size > 0
+            assert np.isfinite(a).all()
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        dumps.append(arrs)
+    for f in dumps[0]:
+        np.testing.assert_allclose(dumps[0][f], dumps[1][f],
+                                   rtol=1e-5, atol=1e-6)
+
+
+def test_bench_rejects_zero_steps():
+    out = subprocess.run(
+        [sys.executable, str(REPO / "bench.py"), "--steps", "0",
+         "--device", "cpu"], capture_output=True, text=True, timeout=120,
+        cwd=REPO)
+    assert out.returncode != 0
+
+
 @pytest.mark.parametrize("par,label,gbatch", [
     ("auto", "dp2", 4),
     ("ddp", "dp2", 4),
