@@ -11,19 +11,23 @@
 
 #define ADAMW_CHUNK 262144  // elements per descriptor chunk
 
-struct AdamWDesc {
-  // int64 fields, laid out to match the host-side [n, 7] int64 tensor
-  int64_t p, g, m, v;  // raw device pointers
-  int64_t n;           // elements in this chunk
-  int64_t p_is_bf16;
-  int64_t g_is_bf16;
-};
+// AdamWDesc (the chunk descriptor) lives in common.h, shared with
+// grad_norm.hip.
 
 typedef __attribute__((ext_vector_type(4))) short s16x4v;
 
+// CLIP=true is global-norm gradient clipping fused into the update: the
+// scale comes from the device-resident total squared grad sum (written by
+// grad_norm.hip) and multiplies g right after the load, before the moment
+// updates — grads are never rewritten and the host never waits.  CLIP=false
+// is the unclipped arithmetic, unchanged.
+template <bool CLIP>
 __global__ void __launch_bounds__(256) adamw_kernel(
     const AdamWDesc* __restrict__ descs, int nchunks, float lr, float beta1,
-    float beta2, float eps, float wd, float inv_bc1, float inv_bc2) {
+    float beta2, float eps, float wd, float inv_bc1, float inv_bc2,
+    const float* __restrict__ sq_total, float max_norm) {
+  float coef = 1.0f;
+  if constexpr (CLIP) coef = clip_coef(sq_total, max_norm);
   for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
     AdamWDesc d = descs[c];
     float* m = (float*)d.m;
@@ -45,6 +49,10 @@ __global__ void __launch_bounds__(256) adamw_kernel(
       } else {
         g4[0] = *reinterpret_cast<const f32x4*>((const float*)d.g + i);
         g4[1] = *reinterpret_cast<const f32x4*>((const float*)d.g + i + 4);
+      }
+      if constexpr (CLIP) {
+        g4[0] *= coef;
+        g4[1] *= coef;
       }
       if (pbf) {
         s16x8 pv = *reinterpret_cast<const s16x8*>((const short*)d.p + i);
@@ -85,6 +93,7 @@ __global__ void __launch_bounds__(256) adamw_kernel(
     // scalar tail
     for (int64_t i = n8 * 8 + threadIdx.x; i < d.n; i += blockDim.x) {
       float g = gbf ? bf2f(((const short*)d.g)[i]) : ((const float*)d.g)[i];
+      if constexpr (CLIP) g *= coef;
       float p = pbf ? bf2f(((const short*)d.p)[i]) : ((const float*)d.p)[i];
       float mi = m[i] = beta1 * m[i] + (1.0f - beta1) * g;
       float vi = v[i] = beta2 * v[i] + (1.0f - beta2) * g * g;
@@ -101,8 +110,19 @@ void adamw_launch(const void* descs, int nchunks, float lr, float beta1,
                   float inv_bc2, hipStream_t s) {
   int grid = nchunks < 16384 ? nchunks : 16384;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, s,
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, s,
                      (const AdamWDesc*)descs, nchunks, lr, beta1, beta2, eps,
-                     wd, inv_bc1, inv_bc2);
+                     wd, inv_bc1, inv_bc2, (const float*)nullptr, 0.0f);
+}
+
+void adamw_launch_clipped(const void* descs, int nchunks, float lr,
+                          float beta1, float beta2, float eps, float wd,
+                          float inv_bc1, float inv_bc2, const float* sq_total,
+                          float max_norm, hipStream_t s) {
+  int grid = nchunks < 16384 ? nchunks : 16384;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid), dim3(256), 0, s,
+                     (const AdamWDesc*)descs, nchunks, lr, beta1, beta2, eps,
+                     wd, inv_bc1, inv_bc2, sq_total, max_norm);
 }
 }

@@ -37,6 +37,10 @@ void ce_bwd_launch(const void*, const int64_t*, const float*, void*, float,
                    int, hipStream_t);
 void adamw_launch(const void*, int, float, float, float, float, float, float,
                   float, hipStream_t);
+void adamw_launch_clipped(const void*, int, float, float, float, float, float,
+                          float, float, const float*, float, hipStream_t);
+void grad_sqsum_launch(const void*, int, float*, float*, int, hipStream_t);
+void grad_scale_launch(const void*, int, const float*, float, hipStream_t);
 void ln_fwd_launch(const void*, const void*, const void*, void*, float*,
                    float*, int64_t, int, float, hipStream_t);
 void ln_bwd_launch(const void*, const void*, const void*, const float*,
@@ -397,6 +401,57 @@ void adamw_step(torch::Tensor descs, int64_t nchunks, double lr, double beta1,
                cur_stream());
 }
 
+#define CHECK_DESCS(descs, nchunks)                                        \
+  TORCH_CHECK((descs).is_cuda() && (descs).dtype() == torch::kLong &&      \
+              (descs).is_contiguous());                                    \
+  TORCH_CHECK((nchunks) >= 0 && (descs).numel() >= 7 * (nchunks),          \
+              "descriptor table shorter than nchunks")
+
+#define CHECK_SQ_TOTAL(t, descs)                                           \
+  TORCH_CHECK((t).is_cuda() && (t).dtype() == torch::kFloat &&             \
+              (t).numel() == 1 && (t).device() == (descs).device(),        \
+              #t " must be a cuda f32 scalar on the descriptors' device")
+
+void adamw_step_clipped(torch::Tensor descs, int64_t nchunks, double lr,
+                        double beta1, double beta2, double eps, double wd,
+                        int64_t step, torch::Tensor sq_total,
+                        double max_norm) {
+  CHECK_DESCS(descs, nchunks);
+  CHECK_SQ_TOTAL(sq_total, descs);
+  const float bc1 = 1.0f - std::pow((float)beta1, (float)step);
+  const float bc2 = 1.0f - std::pow((float)beta2, (float)step);
+  adamw_launch_clipped(descs.data_ptr(), (int)nchunks, (float)lr,
+                       (float)beta1, (float)beta2, (float)eps, (float)wd,
+                       1.0f / bc1, 1.0f / bc2, sq_total.data_ptr<float>(),
+                       (float)max_norm, cur_stream());
+}
+
+// ---------------- global grad norm / clipping ----------------
+void grad_sqsum(torch::Tensor descs, int64_t nchunks, torch::Tensor partials,
+                torch::Tensor out, int64_t slot) {
+  CHECK_DESCS(descs, nchunks);
+  TORCH_CHECK(partials.is_cuda() && partials.dtype() == torch::kFloat &&
+              partials.is_contiguous() && partials.numel() >= nchunks &&
+              partials.device() == descs.device(),
+              "partials must be a cuda f32 buffer of >= nchunks elements");
+  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat &&
+              out.is_contiguous() && out.device() == descs.device() &&
+              slot >= 0 && slot < out.numel(),
+              "out must be a cuda f32 buffer holding `slot`");
+  grad_sqsum_launch(descs.data_ptr(), (int)nchunks,
+                    partials.data_ptr<float>(), out.data_ptr<float>(),
+                    (int)slot, cur_stream());
+}
+
+void grad_scale_(torch::Tensor descs, int64_t nchunks, torch::Tensor sq_total,
+                 double max_norm) {
+  CHECK_DESCS(descs, nchunks);
+  CHECK_SQ_TOTAL(sq_total, descs);
+  grad_scale_launch(descs.data_ptr(), (int)nchunks,
+                    sq_total.data_ptr<float>(), (float)max_norm,
+                    cur_stream());
+}
+
 // ---------------- attention ----------------
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, double scale) {
@@ -464,6 +519,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vocab_start"), py::arg("ignore_index"),
         py::arg("sharded"), py::arg("scale_t") = c10::nullopt);
   m.def("adamw_step", &adamw_step);
+  m.def("adamw_step_clipped", &adamw_step_clipped);
+  m.def("grad_sqsum", &grad_sqsum);
+  m.def("grad_scale_", &grad_scale_);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
 }

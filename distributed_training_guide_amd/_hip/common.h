@@ -119,6 +119,23 @@ __device__ __forceinline__ float block4_sum(float v, float* scratch) {
   return (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
 }
 
+// ---- multi-tensor chunk descriptors (adamw.hip, grad_norm.hip) ----
+// int64 fields, laid out to match the host-side [n, 7] int64 tensor
+struct AdamWDesc {
+  int64_t p, g, m, v;  // raw device pointers
+  int64_t n;           // elements in this chunk
+  int64_t p_is_bf16;
+  int64_t g_is_bf16;
+};
+
+// Global-norm clip scale from the device-resident total squared sum.
+// The compare (not fminf) keeps a NaN total NaN, like torch.clamp(max=1).
+__device__ __forceinline__ float clip_coef(const float* sq_total,
+                                           float max_norm) {
+  float coef = max_norm / (sqrtf(*sq_total) + 1e-6f);
+  return coef > 1.0f ? 1.0f : coef;
+}
+
 #define HIP_CHECK_DEV(expr)                                                  \
   do {                                                                       \
     hipError_t _e = (expr);                                                  \

@@ -35,6 +35,8 @@ LOGGER = logging.getLogger(__name__)
 DEFAULT_CONFIG = {
     "train_micro_batch_size_per_gpu": 1,
     "gradient_accumulation_steps": 1,
+    # global grad-norm clipping (deepspeed's key): 0.0 = off
+    "gradient_clipping": 0.0,
     "bf16": {"enabled": True},
     "zero_optimization": {
         "stage": 3,
@@ -89,7 +91,9 @@ class Engine(torch.nn.Module):
             self.module.parameters(), lr=opt["lr"],
             betas=tuple(opt.get("betas", (0.9, 0.999))),
             eps=opt.get("eps", 1e-8),
-            weight_decay=opt.get("weight_decay", 0.0))
+            weight_decay=opt.get("weight_decay", 0.0),
+            max_grad_norm=config.get("gradient_clipping", 0.0),
+            grad_norm_parts=self.module.grad_norm_parts())
         self.lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             self.optimizer,
             T_max=config["scheduler"]["params"].get("t_max", 1000),

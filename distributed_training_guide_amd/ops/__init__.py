@@ -3,6 +3,7 @@ from .adamw import FusedAdamW
 from .attention import flash_attention
 from .cross_entropy import causal_lm_loss, sharded_causal_lm_loss
 from .fused_linear_ce import fused_causal_lm_loss
+from .grad_clip import clip_grad_norm_, grad_sq_sum
 from .layernorm import LayerNorm, gelu
 from .rmsnorm import RMSNorm, rmsnorm
 from .rope import qkv_rope, rope
@@ -14,6 +15,8 @@ __all__ = [
     "causal_lm_loss",
     "sharded_causal_lm_loss",
     "fused_causal_lm_loss",
+    "clip_grad_norm_",
+    "grad_sq_sum",
     "LayerNorm",
     "gelu",
     "RMSNorm",

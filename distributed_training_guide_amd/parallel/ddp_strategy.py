@@ -29,11 +29,17 @@ class DDPStrategy:
         model = build_model(config, device=self.device, dtype=self.dtype)
         model = DistributedDataParallel(
             model, bucket_cap_mb=getattr(args, "bucket_cap_mb", 128))
+        # grads are complete on every rank after the bucket all-reduce, so
+        # the global clip norm is the plain local one (ZeRO-1 hands its
+        # local optimizer all params for it)
+        max_grad_norm = getattr(args, "max_grad_norm", 0.0)
         if self.use_zero1 and self.world_size > 1:
             optimizer = ZeroRedundancyOptimizer(
-                model.parameters(), optimizer_class=FusedAdamW, lr=args.lr)
+                model.parameters(), optimizer_class=FusedAdamW, lr=args.lr,
+                max_grad_norm=max_grad_norm)
         else:
-            optimizer = FusedAdamW(model.parameters(), lr=args.lr)
+            optimizer = FusedAdamW(model.parameters(), lr=args.lr,
+                                   max_grad_norm=max_grad_norm)
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler

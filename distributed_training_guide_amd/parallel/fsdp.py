@@ -526,6 +526,14 @@ class FSDP(nn.Module):
         return iter([(f"__fsdp_shard__.{u.name}", u.shard)
                      for u in self.units])
 
+    def grad_norm_parts(self):
+        """How a global grad norm is assembled from the flat shards
+        (ops/grad_clip.py `parts`): each rank's squared sum, all-reduced
+        over the shard group.  Shard padding is zero and adds nothing."""
+        group = self.group if self.group is not None else dist.group.WORLD
+        return [(list(self.parameters()),
+                 group if self.world > 1 else None)]
+
     # ---- state dicts ----
     def sharded_state_dict(self):
         return {u.name: u.local_shard_cpu() for u in self.units}

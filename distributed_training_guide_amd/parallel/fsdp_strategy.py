@@ -61,7 +61,10 @@ class FSDPStrategy:
             # full state dict on CPU and broadcasts shards (05:118-126)
             full = model.full_state_dict(rank0_only=True, offload_to_cpu=True)
             model.load_full_state_dict(full, broadcast_from_rank0=True)
-        optimizer = FusedAdamW(model.parameters(), lr=args.lr)
+        optimizer = FusedAdamW(
+            model.parameters(), lr=args.lr,
+            max_grad_norm=getattr(args, "max_grad_norm", 0.0),
+            grad_norm_parts=model.grad_norm_parts())
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler

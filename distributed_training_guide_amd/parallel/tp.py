@@ -378,6 +378,18 @@ class TPLlamaForCausalLM(nn.Module):
             if isinstance(m, RMSNorm):
                 m.weight.register_post_accumulate_grad_hook(hook)
 
+    def grad_norm_parts(self):
+        """How a global grad norm is assembled under TP (ops/grad_clip.py
+        `parts`): the sharded weights' squared sums add over the tp group;
+        the replicated RMSNorm weights count ONCE — their grads are already
+        tp-summed (and so identical on every tp rank) by the hook above."""
+        replicated = {id(m.weight) for m in self.modules()
+                      if isinstance(m, RMSNorm)}
+        sharded = [p for p in self.parameters() if id(p) not in replicated]
+        repl = [p for p in self.parameters() if id(p) in replicated]
+        group = self.mesh.tp_group if self.mesh.tp_size > 1 else None
+        return [(sharded, group), (repl, None)]
+
     def forward(self, input_ids, labels=None, attention_mask=None,
                 position_ids=None, **_):
         g = self.mesh.tp_group

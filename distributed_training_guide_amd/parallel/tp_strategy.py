@@ -39,11 +39,17 @@ class TPStrategy:
         model = TPLlamaForCausalLM(config, self.mesh, device=self.device,
                                    dtype=self.dtype,
                                    loss_parallel=self.loss_parallel)
+        # tp-aware clip norm; DDP's dp all-reduce leaves the grads
+        # identical across dp replicas, so the parts hold with or without it
+        norm_parts = model.grad_norm_parts()
         if self.mesh.dp_size > 1:
             model = DistributedDataParallel(
                 model, bucket_cap_mb=getattr(args, "bucket_cap_mb", 128),
                 process_group=self.mesh.dp_group)
-        optimizer = FusedAdamW(model.parameters(), lr=args.lr)
+        optimizer = FusedAdamW(
+            model.parameters(), lr=args.lr,
+            max_grad_norm=getattr(args, "max_grad_norm", 0.0),
+            grad_norm_parts=norm_parts)
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler
@@ -134,6 +140,15 @@ class TwoDStrategy(TPStrategy):
         super().__init__(args, tp_size=getattr(args, "tensor_parallel", 8))
 
     def build(self, config, args):
+        if getattr(args, "max_grad_norm", 0.0) > 0:
+            # an FSDP flat shard of a tp-local model mixes tp-sharded and
+            # tp-replicated elements: an exact global norm needs a
+            # per-offset mask, which is not implemented
+            raise ValueError(
+                "--max-grad-norm is not supported with 2D (FSDP x TP) "
+                "parallelism: a flat shard mixes tp-sharded and "
+                "tp-replicated gradients, so the global norm cannot be "
+                "assembled per part")
         model = TPLlamaForCausalLM(config, self.mesh, device=self.device,
                                    dtype=self.dtype,
                                    loss_parallel=self.loss_parallel)

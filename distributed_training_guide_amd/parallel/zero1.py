@@ -44,6 +44,10 @@ class ZeroRedundancyOptimizer(torch.optim.Optimizer):
             self.partitions[r].append(params[i])
             loads[r] += params[i].numel()
 
+        if kwargs.get("max_grad_norm", 0.0) > 0:
+            # only the moments are partitioned: every rank holds every
+            # grad, so the clip norm runs over ALL params, not the partition
+            kwargs.setdefault("grad_norm_parts", [(params, None)])
         self.local_opt = optimizer_class(self.partitions[self.rank], **kwargs)
         # delegate Optimizer surface to the local optimizer (schedulers
         # mutate param_groups[...]["lr"] in place)
@@ -90,6 +94,12 @@ class ZeroRedundancyOptimizer(torch.optim.Optimizer):
                     p.view(-1).copy_(shard[off: off + p.numel()])
                     off += p.numel()
         return loss
+
+    @property
+    def last_grad_norm(self):
+        """Pre-clip global grad norm of the last clipped step (see
+        FusedAdamW); None without max_grad_norm."""
+        return getattr(self.local_opt, "last_grad_norm", None)
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self._all_params:

@@ -52,6 +52,9 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
         p.add_argument("--max-steps", default=0, type=int,
                        help="stop after N optimizer steps (0 = unlimited)")
         p.add_argument("--grad-accum-steps", default=1, type=int)
+        p.add_argument("--max-grad-norm", default=0.0, type=float,
+                       help="clip the global gradient norm to this value, "
+                            "fused into the AdamW update (0 = off)")
         p.add_argument("--deterministic", action="store_true")
         p.add_argument("--wandb", action="store_true")
         p.add_argument("--wandb-mode", default="rank0",
@@ -236,6 +239,10 @@ def run_training(args, strategy):
                     **{f"time/{k}": t.avg_elapsed_ms()
                        for k, t in timers.items()},
                 }
+                if getattr(args, "max_grad_norm", 0.0) > 0:
+                    # pre-clip global norm of the last step; the only sync
+                    # clipping adds, next to loss.item()'s
+                    info["grad_norm"] = optimizer.last_grad_norm.item()
                 LOGGER.info(info)
                 if wandb_run is not None:
                     wandb_run.log(info, step=state["global_step"])
