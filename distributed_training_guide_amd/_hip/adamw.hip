@@ -8,6 +8,7 @@
 // bf16 or fp32; grads bf16 or fp32 (fp32 under FSDP's reduce_dtype=fp32).
 // Decoupled weight decay (AdamW): p *= (1 - lr*wd) before the Adam update.
 #include "common.h"
+#include "launchers.h"
 
 #define ADAMW_CHUNK 262144  // elements per descriptor chunk
 

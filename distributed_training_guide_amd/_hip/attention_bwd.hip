@@ -27,6 +27,7 @@
 //   B[k][n]: lane l -> n = l&15, k = (l>>4)*8 + j
 //   C/D    : lane l -> n = l&15, m = (l>>4)*4 + r
 #include "common.h"
+#include "launchers.h"
 
 using bf16x8 = s16x8;
 #define LOG2E 1.4426950408889634f

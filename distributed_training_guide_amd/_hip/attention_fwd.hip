@@ -38,6 +38,7 @@
 //   B[k][n]: lane l holds n = l&15, k = (l>>4)*8 + j
 //   C/D     : lane l holds n = l&15, m = (l>>4)*4 + r (r=0..3)
 #include "common.h"
+#include "launchers.h"
 
 using bf16x8 = s16x8;
 typedef __attribute__((ext_vector_type(2))) short s16x2;

@@ -5,59 +5,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
-extern "C" {
-void rmsnorm_fwd_launch(const void*, const void*, void*, void*, int64_t, int,
-                        float, hipStream_t);
-void rmsnorm_bwd_launch(const void*, const void*, const void*, const void*,
-                        void*, float*, void*, int, int64_t, int, hipStream_t);
-void qkv_rope_fwd_launch(const void*, void*, void*, void*, const float*,
-                         const float*, const int*, int64_t, int, int, int,
-                         int, hipStream_t);
-void qkv_rope_bwd_launch(const void*, const void*, const void*, void*,
-                         const float*, const float*, const int*, int64_t,
-                         int, int, int, int, hipStream_t);
-void add_rmsnorm_fwd_launch(const void*, const void*, const void*, void*,
-                            void*, void*, int64_t, int, float, hipStream_t);
-void add_rmsnorm_bwd_launch(const void*, const void*, const void*,
-                            const void*, const void*, void*, float*, void*,
-                            int, int64_t, int, hipStream_t);
-void rmsnorm_dw_reduce_launch(const float*, void*, int, int, hipStream_t);
-void rope_launch(const void*, void*, const float*, const float*, const int*,
-                 int64_t, int, int, int, int, hipStream_t);
-void silu_mul_fwd_launch(const void*, void*, int64_t, int, hipStream_t);
-void silu_mul_bwd_launch(const void*, const void*, void*, int64_t, int,
-                         hipStream_t);
-void ce_fwd_launch(const void*, const int64_t*, float*, float*, int64_t, int,
-                   int, int, int64_t, hipStream_t);
-void ce_fwd_sharded_launch(const void*, const int64_t*, float*, float*, float*,
-                           int64_t, int, int, int, int64_t, int64_t,
-                           hipStream_t);
-void ce_bwd_launch(const void*, const int64_t*, const float*, void*, float,
-                   const float*, int64_t, int, int, int, int64_t, int64_t,
-                   int, hipStream_t);
-void adamw_launch(const void*, int, float, float, float, float, float, float,
-                  float, hipStream_t);
-void adamw_launch_clipped(const void*, int, float, float, float, float, float,
-                          float, float, const float*, float, hipStream_t);
-void grad_sqsum_launch(const void*, int, float*, float*, int, hipStream_t);
-void grad_scale_launch(const void*, int, const float*, float, hipStream_t);
-void ln_fwd_launch(const void*, const void*, const void*, void*, float*,
-                   float*, int64_t, int, float, hipStream_t);
-void ln_bwd_launch(const void*, const void*, const void*, const float*,
-                   const float*, void*, float*, float*, void*, void*, int,
-                   int64_t, int, hipStream_t);
-void gelu_fwd_launch(const void*, void*, int64_t, hipStream_t);
-void gelu_bwd_launch(const void*, const void*, void*, int64_t, hipStream_t);
-void embed_fwd_launch(const void*, const int64_t*, void*, int64_t, int,
-                      int64_t, hipStream_t);
-void embed_bwd_launch(const void*, const int64_t*, float*, void*, int64_t,
-                      int, int64_t, hipStream_t);
-void attn_fwd_launch(const void*, const void*, const void*, void*, float*,
-                     int, int, int, int, int, float, hipStream_t);
-void attn_bwd_launch(const void*, const void*, const void*, const void*,
-                     const void*, const float*, float*, void*, void*, void*,
-                     int, int, int, int, int, float, hipStream_t);
-}
+#include "launchers.h"
 
 namespace {
 
@@ -69,6 +17,14 @@ inline hipStream_t cur_stream() {
   TORCH_CHECK((t).is_cuda(), #t " must be on the GPU");               \
   TORCH_CHECK((t).dtype() == torch::kBFloat16, #t " must be bf16");   \
   TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
+
+// [nblocks, H] f32 per-block partials of a norm backward, plus the
+// COLSUM_RY tail rows colsum_launch folds them through
+inline torch::Tensor alloc_partials(int nblocks, int H,
+                                    const torch::Tensor& like) {
+  return torch::empty({(int64_t)nblocks + COLSUM_RY, (int64_t)H},
+                      like.options().dtype(torch::kFloat));
+}
 
 // ---------------- rmsnorm ----------------
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
@@ -93,8 +49,7 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
   const int nblocks = (int)std::min<int64_t>(nrows, 2048);
   auto dx = torch::empty_like(x);
   auto dw = torch::empty_like(w);
-  auto dw_partial =
-      torch::empty({(int64_t)nblocks, (int64_t)H}, x.options().dtype(torch::kFloat));
+  auto dw_partial = alloc_partials(nblocks, H, x);
   rmsnorm_bwd_launch(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
                      rstd.data_ptr(), dx.data_ptr(),
                      dw_partial.data_ptr<float>(), dw.data_ptr(), nblocks,
@@ -157,9 +112,7 @@ std::vector<torch::Tensor> add_rmsnorm_bwd(torch::Tensor dy,
   const int nblocks = (int)std::min<int64_t>(nrows, 2048);
   auto dx = torch::empty_like(res_out);
   auto dw = torch::empty_like(w);
-  auto dw_partial =
-      torch::empty({(int64_t)nblocks, (int64_t)H},
-                   res_out.options().dtype(torch::kFloat));
+  auto dw_partial = alloc_partials(nblocks, H, res_out);
   add_rmsnorm_bwd_launch(dy.data_ptr(), dres_out.data_ptr(),
                          res_out.data_ptr(), w.data_ptr(), rstd.data_ptr(),
                          dx.data_ptr(), dw_partial.data_ptr<float>(),
@@ -299,9 +252,8 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   auto dx = torch::empty_like(x);
   auto dw = torch::empty_like(w);
   auto db = torch::empty_like(w);
-  auto opts = x.options().dtype(torch::kFloat);
-  auto dw_partial = torch::empty({(int64_t)nblocks, (int64_t)H}, opts);
-  auto db_partial = torch::empty({(int64_t)nblocks, (int64_t)H}, opts);
+  auto dw_partial = alloc_partials(nblocks, H, x);
+  auto db_partial = alloc_partials(nblocks, H, x);
   ln_bwd_launch(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
                 mu.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(),
                 dw_partial.data_ptr<float>(), db_partial.data_ptr<float>(),

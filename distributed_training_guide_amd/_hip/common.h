@@ -136,11 +136,11 @@ __device__ __forceinline__ float clip_coef(const float* sq_total,
   return coef > 1.0f ? 1.0f : coef;
 }
 
-#define HIP_CHECK_DEV(expr)                                                  \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) return _e;                                         \
-  } while (0)
+// Grid of the row-per-block norm kernels (host side): one block per row up
+// to 2048, past which the kernels grid-stride; never an empty grid.
+inline int row_grid(int64_t nrows) {
+  return (int)(nrows < 1 ? 1 : nrows < 2048 ? nrows : 2048);
+}
 
 // ---- attention kernel shared idioms (fwd v3 / bwd v2) ----
 // pack two f32 into one reg of 2 bf16 (no builtin on gfx950)

@@ -15,6 +15,7 @@
 // Python side all-reduces the three scalars per token over the TP group and
 // finishes the loss — see ops/cross_entropy.py.
 #include "common.h"
+#include "launchers.h"
 
 // one block per row, online max/sum in a single pass
 template <bool SHARDED>

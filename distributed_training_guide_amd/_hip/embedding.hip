@@ -9,6 +9,7 @@
 //      packed atomics would round-to-nearest per add and bias heavy
 //      hitters), then convert once to the bf16 grad.
 #include "common.h"
+#include "launchers.h"
 
 __global__ void __launch_bounds__(256) embed_fwd_kernel(
     const short* __restrict__ table, const int64_t* __restrict__ ids,

@@ -13,6 +13,7 @@
 // a DDP bucket, buf[1:]) is supported: a scalar head is peeled up to the
 // next 16 B boundary before the 8-element vector body.
 #include "common.h"
+#include "launchers.h"
 
 // elements to peel so that (base + head) is 16 B aligned (base is
 // element-aligned), clamped to the chunk length

@@ -1,0 +1,112 @@
+// C-linkage entry points of the HIP extension, declared once.
+//
+// bindings.cpp calls these; every .hip file that defines one includes this
+// header, so a definition that drifts from its declaration is a compile
+// error (conflicting types for a C-linkage function) rather than a call
+// that links and passes garbage.  bf16 tensors travel as void*.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// colsum_launch folds its input in two stages through COLSUM_RY rows of
+// f32 scratch.  Every `partial` buffer below is
+// [nblocks + COLSUM_RY, H] f32: the kernels write rows [0, nblocks), the
+// tail is that scratch.
+#define COLSUM_RY 16
+
+extern "C" {
+// colsum.hip: out[H] (bf16) = column sums of partial[0:nblocks, H]
+void colsum_launch(float* partial, void* out, int nblocks, int H,
+                   hipStream_t s);
+
+// rmsnorm.hip
+void rmsnorm_fwd_launch(const void* x, const void* w, void* y, void* rstd,
+                        int64_t nrows, int H, float eps, hipStream_t s);
+void rmsnorm_bwd_launch(const void* dy, const void* x, const void* w,
+                        const void* rstd, void* dx, float* dw_partial,
+                        void* dw, int nblocks, int64_t nrows, int H,
+                        hipStream_t s);
+void add_rmsnorm_fwd_launch(const void* res, const void* delta, const void* w,
+                            void* res_out, void* y, void* rstd, int64_t nrows,
+                            int H, float eps, hipStream_t s);
+void add_rmsnorm_bwd_launch(const void* dy, const void* dres_out,
+                            const void* x, const void* w, const void* rstd,
+                            void* dx, float* dw_partial, void* dw,
+                            int nblocks, int64_t nrows, int H,
+                            hipStream_t s);
+
+// layernorm.hip
+void ln_fwd_launch(const void* x, const void* w, const void* b, void* y,
+                   float* mu, float* rstd, int64_t nrows, int H, float eps,
+                   hipStream_t s);
+void ln_bwd_launch(const void* dy, const void* x, const void* w,
+                   const float* mu, const float* rstd, void* dx,
+                   float* dw_partial, float* db_partial, void* dw, void* db,
+                   int nblocks, int64_t nrows, int H, hipStream_t s);
+void gelu_fwd_launch(const void* x, void* y, int64_t n, hipStream_t s);
+void gelu_bwd_launch(const void* dy, const void* x, void* dx, int64_t n,
+                     hipStream_t s);
+
+// rope.hip, qkv_rope.hip
+void rope_launch(const void* x, void* y, const float* cs, const float* sn,
+                 const int* positions, int64_t total_rows, int S, int H, int D,
+                 int backward, hipStream_t stream);
+void qkv_rope_fwd_launch(const void* qkv, void* q, void* k, void* v,
+                         const float* cs, const float* sn,
+                         const int* positions, int64_t BS, int S, int Hq,
+                         int Hkv, int D, hipStream_t stream);
+void qkv_rope_bwd_launch(const void* dq, const void* dk, const void* dv,
+                         void* dqkv, const float* cs, const float* sn,
+                         const int* positions, int64_t BS, int S, int Hq,
+                         int Hkv, int D, hipStream_t stream);
+
+// silu_mul.hip
+void silu_mul_fwd_launch(const void* gu, void* y, int64_t nrows, int I,
+                         hipStream_t s);
+void silu_mul_bwd_launch(const void* dy, const void* gu, void* dgu,
+                         int64_t nrows, int I, hipStream_t s);
+
+// embedding.hip
+void embed_fwd_launch(const void* table, const int64_t* ids, void* out,
+                      int64_t nrows, int H, int64_t V, hipStream_t s);
+void embed_bwd_launch(const void* dy, const int64_t* ids, float* acc,
+                      void* dtable, int64_t nrows, int H, int64_t V,
+                      hipStream_t s);
+
+// cross_entropy.hip
+void ce_fwd_launch(const void* logits, const int64_t* labels, float* loss,
+                   float* lse, int64_t nrows, int S_logits, int S_out, int V,
+                   int64_t ignore_index, hipStream_t st);
+void ce_fwd_sharded_launch(const void* logits, const int64_t* labels,
+                           float* maxout, float* sumout, float* gathered,
+                           int64_t nrows, int S_logits, int S_out, int V,
+                           int64_t vocab_start, int64_t ignore_index,
+                           hipStream_t st);
+void ce_bwd_launch(const void* logits, const int64_t* labels, const float* lse,
+                   void* dlogits, float scale, const float* scale_ptr,
+                   int64_t nrows, int S_logits, int S_out, int V,
+                   int64_t vocab_start, int64_t ignore_index, int sharded,
+                   hipStream_t st);
+
+// adamw.hip, grad_norm.hip
+void adamw_launch(const void* descs, int nchunks, float lr, float beta1,
+                  float beta2, float eps, float wd, float inv_bc1,
+                  float inv_bc2, hipStream_t s);
+void adamw_launch_clipped(const void* descs, int nchunks, float lr,
+                          float beta1, float beta2, float eps, float wd,
+                          float inv_bc1, float inv_bc2, const float* sq_total,
+                          float max_norm, hipStream_t s);
+void grad_sqsum_launch(const void* descs, int nchunks, float* partials,
+                       float* out, int slot, hipStream_t s);
+void grad_scale_launch(const void* descs, int nchunks, const float* sq_total,
+                       float max_norm, hipStream_t s);
+
+// attention_fwd.hip, attention_bwd.hip
+void attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
+                     float* lse, int B, int S, int Hq, int Hkv, int D,
+                     float scale, hipStream_t stream);
+void attn_bwd_launch(const void* dout, const void* q, const void* k,
+                     const void* v, const void* o, const float* lse,
+                     float* delta, void* dq, void* dk, void* dv, int B, int S,
+                     int Hq, int Hkv, int D, float scale, hipStream_t stream);
+}

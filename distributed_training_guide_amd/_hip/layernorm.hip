@@ -3,8 +3,8 @@
 // LayerNorm/GELU come from transformers; SURVEY.md §2b "torch.compile
 // fusions").  Same machinery as rmsnorm.hip: one workgroup per row,
 // bf16x8 vector loads, f32 accumulation, register dw/db accumulators
-// spilled once per block; the [nblocks,H] partials are reduced by the
-// rmsnorm two-stage reducer.
+// spilled once per block; the [nblocks,H] partials are reduced by
+// colsum.hip.
 //
 //   y  = (x - mu) * rstd * w + b,   rstd = rsqrt(var + eps)
 //   dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * w
@@ -12,6 +12,7 @@
 //
 //   gelu(x) = 0.5 x (1 + tanh(k (x + 0.044715 x^3))), k = sqrt(2/pi)
 #include "common.h"
+#include "launchers.h"
 
 #define GELU_K 0.7978845608028654f
 #define GELU_C 0.044715f
@@ -227,13 +228,10 @@ __global__ void __launch_bounds__(256) gelu_bwd_kernel(
 }
 
 extern "C" {
-void rmsnorm_dw_reduce_launch(const float*, void*, int, int, hipStream_t);
-
 void ln_fwd_launch(const void* x, const void* w, const void* b, void* y,
                    float* mu, float* rstd, int64_t nrows, int H, float eps,
                    hipStream_t s) {
-  int grid = (int)(nrows < 2048 ? (nrows < 1 ? 1 : nrows) : 2048);
-  hipLaunchKernelGGL(ln_fwd_kernel, dim3(grid), dim3(256), 0, s,
+  hipLaunchKernelGGL(ln_fwd_kernel, dim3(row_grid(nrows)), dim3(256), 0, s,
                      (const short*)x, (const short*)w, (const short*)b,
                      (short*)y, mu, rstd, nrows, H, eps);
 }
@@ -250,8 +248,8 @@ void ln_bwd_launch(const void* dy, const void* x, const void* w,
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(nblocks), dim3(256), shmem, s,
                      (const short*)dy, (const short*)x, (const short*)w, mu,
                      rstd, (short*)dx, dw_partial, db_partial, nrows, H);
-  rmsnorm_dw_reduce_launch(dw_partial, dw, nblocks, H, s);
-  rmsnorm_dw_reduce_launch(db_partial, db, nblocks, H, s);
+  colsum_launch(dw_partial, dw, nblocks, H, s);
+  colsum_launch(db_partial, db, nblocks, H, s);
 }
 
 void gelu_fwd_launch(const void* x, void* y, int64_t n, hipStream_t s) {

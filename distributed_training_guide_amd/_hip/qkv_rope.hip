@@ -8,6 +8,7 @@
 // Layouts: qkv [B,S,W] bf16, W = (Hq+2*Hkv)*D; q [B,S,Hq,D];
 // k/v [B,S,Hkv,D]; cos/sin f32 [max_pos, D/2]; positions int32 [S] or null.
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;
 

@@ -12,6 +12,7 @@
 // `positions` (optional, int32 [S]) supplies absolute positions when the
 // sequence is sharded (sequence parallelism) or offset (resume mid-sequence).
 #include "common.h"
+#include "launchers.h"
 
 template <bool BWD>
 __global__ void __launch_bounds__(256) rope_kernel(

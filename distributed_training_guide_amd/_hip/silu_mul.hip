@@ -10,6 +10,7 @@
 //
 //   silu(x) = x * sigmoid(x);  d/dx silu = sigmoid(x) * (1 + x * (1 - sigmoid(x)))
 #include "common.h"
+#include "launchers.h"
 
 __global__ void __launch_bounds__(256) silu_mul_fwd_kernel(
     const short* __restrict__ gu, short* __restrict__ y, int64_t nrows,

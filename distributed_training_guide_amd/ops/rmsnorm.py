@@ -52,7 +52,7 @@ class RMSNorm(torch.nn.Module):
 
 
 class _AddRMSNormFn(torch.autograd.Function):
-    """Fused residual-add + RMSNorm (add_rmsnorm.hip): res_out = res+delta,
+    """Fused residual-add + RMSNorm (rmsnorm.hip): res_out = res+delta,
     y = rmsnorm(res_out)*w in one pass; backward folds the downstream
     residual gradient into dx (no separate elementwise adds)."""
 

@@ -6,7 +6,12 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("rows,H", [(512, 768), (1000, 1600), (64, 104)])
+@pytest.mark.parametrize("rows,H", [
+    (512, 768), (1000, 1600), (64, 104),
+    (3, 100),    # H % 8 != 0: scalar path
+    (2100, 64),  # > 2048 rows: a block folds two rows into one partial
+    (2, 8200),   # H > 8192: past the register accumulators, scalar fallback
+])
 def test_layernorm_matches_fp32(rows, H):
     from distributed_training_guide_amd.ops.layernorm import LayerNorm
 

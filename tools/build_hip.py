@@ -6,8 +6,8 @@ torch bindings with hipcc (no hipify, no CUDA path), links them into
 distributed_training_guide_amd/_C.so.  hipcc cross-compiles gfx950 without a
 GPU present, so this runs anywhere the ROCm toolchain exists.
 
-Incremental: objects are rebuilt only when their source (or common.h) is
-newer.  Kernel files compile in parallel.
+Incremental: objects are rebuilt only when their source (or any _hip/*.h)
+is newer.  Kernel files compile in parallel.
 """
 import concurrent.futures as cf
 import os
@@ -54,7 +54,7 @@ def _needs_build(src: Path, obj: Path, extra_deps=()):
     if not obj.exists():
         return True
     mt = obj.stat().st_mtime
-    deps = [src, HIP_DIR / "common.h", *extra_deps]
+    deps = [src, *HIP_DIR.glob("*.h"), *extra_deps]
     return any(d.exists() and d.stat().st_mtime > mt for d in deps)
 
 
