@@ -71,12 +71,20 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(
 }
 
 // ---------------- dk / dv ----------------
+// DOC (both kernels below) adds the intra-document mask of packed rows; see
+// attention_fwd.hip.  Each kernel reads the table that is lane-local in its
+// fragment layout: dkdv owns keys, so it reads doc_end [B,S] int32 (the
+// exclusive end of each key's document; q row i sees key j iff
+// j <= i < doc_end[b,j]); dq owns q rows and reads doc_start like the
+// forward.  DOC=false is the plain causal kernel (table unused, may be
+// null).
+template <bool DOC>
 __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
     const short* __restrict__ dout, const short* __restrict__ q,
     const short* __restrict__ k, const short* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
     short* __restrict__ dk, short* __restrict__ dv, int B, int S, int Hq,
-    int Hkv, int D, float scale) {
+    int Hkv, int D, float scale, const int* __restrict__ doc_end) {
   // double-buffered ROW-major staging of the 64-q-row tile (q[qrow][d],
   // dO[qrow][d], st_idx subtile image): serves BOTH the Q/dO A-fragments
   // (b128 row reads, replacing per-tile global gathers) and the
@@ -146,7 +154,22 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
 
   // iteration space: (h in gqa group) x (64-row q tiles >= causal start)
   const int qstart = kt * 64;
-  const int nqt = (S - qstart + 63) / 64;
+  // DOC: this lane's key stops being visible at dend (clamped like the
+  // key); dend_min is the smallest of the wave's 16 (its first key's —
+  // doc_end is monotone), below which no q row needs the document test.
+  // No q row at or past the end of the block's last valid key's document
+  // sees any of the block's keys, so the q-tile walk stops there instead
+  // of at S.
+  int dend = S, dend_min = S, qcap = S;
+  if (DOC) {
+    const int* deb = doc_end + (int64_t)b * S;
+    dend = deb[min(kv0 + l15, S - 1)];
+    dend_min = deb[min(kv0, S - 1)];
+    // clamped to the contract (j < doc_end[j] <= S): a bad table cannot
+    // move the staging loads out of bounds
+    qcap = min(max(deb[min(qstart + 63, S - 1)], qstart + 1), S);
+  }
+  const int nqt = (qcap - qstart + 63) / 64;
   const int niter = group * nqt;
 
   // staging via LDS-DMA (st_idx subtile image;
@@ -222,7 +245,10 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
     // P = exp(scale*S - lse), dS = scale*P*(dP - delta), packed into
     // A-operand order — only one mt of S/dP state stays live ----
     const int key = kv0 + l15;  // this lane's key (C n-position)
-    const bool diag = (qt < kt * 64 + 64) || (qt + 63 >= S);
+    // DOC also masks on every tile that reaches the end of the document
+    // of the wave's first key
+    const bool diag = (qt < kt * 64 + 64) || (qt + 63 >= S) ||
+                      (DOC && qt + 63 >= dend_min);
     u32x4 pk_p[2], pk_ds[2];
     __builtin_amdgcn_s_setprio(1);  // T5: prioritize the MFMA stream
 #pragma unroll
@@ -260,7 +286,9 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
           const int qloc = qoff + r;
           const int qrow = qt + qloc;
           float e = (scale * sa[r] - lse_lds[buf][qloc]) * LOG2E;
-          if (diag && (key > qrow || qrow >= S || key >= S)) e = -INFINITY;
+          if (diag && (key > qrow || qrow >= S || key >= S ||
+                       (DOC && qrow >= dend)))
+            e = -INFINITY;
           p[r] = exp2f(e);
           ds[r] = scale * p[r] * (da[r] - del_lds[buf][qloc]);
         }
@@ -309,12 +337,13 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
 }
 
 // ---------------- dq ----------------
+template <bool DOC>
 __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
     const short* __restrict__ dout, const short* __restrict__ q,
     const short* __restrict__ k, const short* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
     short* __restrict__ dq, int B, int S, int Hq, int Hkv, int D,
-    float scale) {
+    float scale, const int* __restrict__ doc_start) {
   // double-buffered K and V tiles (st_idx subtile image): K serves
   // the S^T A-fragments (b128 row reads) AND the dQ B-fragments (tr16
   // transpose reads); V serves the dP^T A-fragments
@@ -393,6 +422,21 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
   const int kv_end = min(S, qtile * 128 + 128);
   const int ntiles = (kv_end + 63) / 64;
 
+  // DOC: per-lane first visible key of each q row, the row group's largest
+  // one (its last valid row) for the wave-uniform diag test, and the
+  // block's first K/V tile — as in attention_fwd.hip
+  int dstart[2] = {0, 0}, dsmax[2] = {0, 0};
+  int t0 = 0;
+  if (DOC) {
+    const int* dsb = doc_start + (int64_t)b * S;
+#pragma unroll
+    for (int nq = 0; nq < 2; ++nq) {
+      dstart[nq] = dsb[min(rowb[nq] + l15, S - 1)];
+      dsmax[nq] = dsb[min(rowb[nq] + 15, S - 1)];
+    }
+    t0 = min(max(dsb[qtile * 128], 0), qtile * 128) / 64;  // in bounds
+  }
+
   // LDS-DMA staging (global_load_lds; see attention_fwd.hip)
   const int nslot = D >> 3;
   const int ncw = nslot >> 2;
@@ -421,12 +465,14 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
     }
   };
 
-  stage_k(0, 0);
+  // the first tile visited lands in buffer 0 whatever its parity: the
+  // buffer index counts from t0, not from tile 0
+  stage_k(t0 * 64, 0);
   __syncthreads();
 
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = t0; t < ntiles; ++t) {
     const int kv0 = t * 64;
-    const int buf = t & 1;
+    const int buf = (t - t0) & 1;
     if (t + 1 < ntiles) stage_k((t + 1) * 64, buf ^ 1);
 
     // group 0 (lower rows) drops out at the final diagonal tiles; group 1
@@ -467,7 +513,8 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
 #pragma unroll
         for (int nq = 0; nq < 2; ++nq) {
           const int qrow = rowb[nq] + l15;
-          const bool diag = (kv0 + 63 > rowb[nq]) || smask;
+          const bool diag = (kv0 + 63 > rowb[nq]) || smask ||
+                            (DOC && dsmax[nq] > kv0);
           const f32x4 sv = nq ? s1 : s0;
           const f32x4 dv = nq ? d1 : d0;
           float ds[4];
@@ -475,7 +522,8 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
           for (int r = 0; r < 4; ++r) {
             const int keyr = kv0 + koff + r;
             float e = (scale * sv[r] - lse_r[nq]) * LOG2E;
-            if (diag && (keyr > qrow || keyr >= S || qrow >= S))
+            if (diag && (keyr > qrow || keyr >= S || qrow >= S ||
+                         (DOC && keyr < dstart[nq])))
               e = -INFINITY;
             float p = exp2f(e);
             ds[r] = scale * p * (dv[r] - del_r[nq]);
@@ -528,25 +576,49 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
   }
 }
 
-extern "C" {
-void attn_bwd_launch(const void* dout, const void* q, const void* k,
-                     const void* v, const void* o, const float* lse,
-                     float* delta, void* dq, void* dk, void* dv, int B, int S,
-                     int Hq, int Hkv, int D, float scale, hipStream_t stream) {
+namespace {
+template <bool DOC>
+void bwd_launch(const void* dout, const void* q, const void* k, const void* v,
+                const void* o, const float* lse, float* delta, void* dq,
+                void* dk, void* dv, const int* doc_start, const int* doc_end,
+                int B, int S, int Hq, int Hkv, int D, float scale,
+                hipStream_t stream) {
   int64_t nrows = (int64_t)B * S * Hq;
   int64_t dwant = (nrows + 15) / 16;
   int dgrid = (int)(dwant < 2048 ? (dwant < 1 ? 1 : dwant) : 2048);
   hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, stream,
                      (const short*)dout, (const short*)o, delta, B, S, Hq, D);
   int nkt = (S + 63) / 64;
-  hipLaunchKernelGGL(attn_dkdv_kernel, dim3((uint32_t)((int64_t)B * Hkv * nkt)),
-                     dim3(256), 0, stream, (const short*)dout, (const short*)q,
+  hipLaunchKernelGGL(attn_dkdv_kernel<DOC>,
+                     dim3((uint32_t)((int64_t)B * Hkv * nkt)), dim3(256), 0,
+                     stream, (const short*)dout, (const short*)q,
                      (const short*)k, (const short*)v, lse, delta, (short*)dk,
-                     (short*)dv, B, S, Hq, Hkv, D, scale);
+                     (short*)dv, B, S, Hq, Hkv, D, scale, doc_end);
   int ntq = (S + 127) / 128;
-  hipLaunchKernelGGL(attn_dq_kernel, dim3((uint32_t)((int64_t)B * Hq * ntq)),
-                     dim3(256), 0, stream, (const short*)dout, (const short*)q,
+  hipLaunchKernelGGL(attn_dq_kernel<DOC>,
+                     dim3((uint32_t)((int64_t)B * Hq * ntq)), dim3(256), 0,
+                     stream, (const short*)dout, (const short*)q,
                      (const short*)k, (const short*)v, lse, delta, (short*)dq,
-                     B, S, Hq, Hkv, D, scale);
+                     B, S, Hq, Hkv, D, scale, doc_start);
+}
+}  // namespace
+
+extern "C" {
+void attn_bwd_launch(const void* dout, const void* q, const void* k,
+                     const void* v, const void* o, const float* lse,
+                     float* delta, void* dq, void* dk, void* dv, int B, int S,
+                     int Hq, int Hkv, int D, float scale, hipStream_t stream) {
+  bwd_launch<false>(dout, q, k, v, o, lse, delta, dq, dk, dv, nullptr, nullptr,
+                    B, S, Hq, Hkv, D, scale, stream);
+}
+
+void attn_bwd_doc_launch(const void* dout, const void* q, const void* k,
+                         const void* v, const void* o, const float* lse,
+                         float* delta, void* dq, void* dk, void* dv,
+                         const int* doc_start, const int* doc_end, int B,
+                         int S, int Hq, int Hkv, int D, float scale,
+                         hipStream_t stream) {
+  bwd_launch<true>(dout, q, k, v, o, lse, delta, dq, dk, dv, doc_start,
+                   doc_end, B, S, Hq, Hkv, D, scale, stream);
 }
 }

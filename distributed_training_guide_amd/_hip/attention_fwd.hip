@@ -7,7 +7,9 @@
 // SURVEY.md §2b "Flash attention 2").
 //
 // Layout: q [B,S,Hq,D], k/v [B,S,Hkv,D] bf16 contiguous (BSHD). GQA via
-// Hq % Hkv == 0. Causal always. Saves lse [B,Hq,S] f32 for the backward.
+// Hq % Hkv == 0. Causal always; the DOC instantiation additionally confines
+// each query to its own document of a packed row (flash-attn-2's varlen
+// masking). Saves lse [B,Hq,S] f32 for the backward.
 //
 // v3 design (guide §5.5 / §5 "common mistakes"):
 //   * S^T = mfma(A=K, B=Q): the C fragment then holds qrow = lane&15 —
@@ -52,11 +54,16 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
 #define KVBLK 64   // keys per LDS tile
 #define LOG2E 1.4426950408889634f
 
+// DOC adds the intra-document mask of packed rows: doc_start [B,S] int32
+// holds, per token, the index of the first token of its document; query i
+// sees key j iff doc_start[b,i] <= j <= i.  DOC=false is the plain causal
+// kernel (doc_start unused, may be null).
+template <bool DOC>
 __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, short* __restrict__ o,
     float* __restrict__ lse_out, int B, int S, int Hq, int Hkv, int D,
-    float scale) {
+    float scale, const int* __restrict__ doc_start) {
   // both tiles in the 16-col-subtile image (st_idx; conflict-free tr16
   // reads + b128 row reads), double-buffered
   __shared__ short k_lds[2][KVBLK * 128];
@@ -149,6 +156,24 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   const float c = scale * LOG2E;
   (void)hkv;
 
+  // DOC: per-lane first visible key of each q row (clamped like qrow), the
+  // row group's largest one (its last valid row — doc_start is monotone)
+  // for the wave-uniform need_mask test, and the block's first K/V tile:
+  // no row of the q tile sees a key before its first row's document.
+  int dstart[2] = {0, 0}, dsmax[2] = {0, 0};
+  int t0 = 0;
+  if (DOC) {
+    const int* dsb = doc_start + (int64_t)b * S;
+#pragma unroll
+    for (int nq = 0; nq < 2; ++nq) {
+      dstart[nq] = dsb[min(rowb[nq] + l15, S - 1)];
+      dsmax[nq] = dsb[min(rowb[nq] + 15, S - 1)];
+    }
+    // clamped to the contract (0 <= doc_start[i] <= i) so that a bad table
+    // cannot move the staging loads out of bounds
+    t0 = min(max(dsb[qtile * QBLK], 0), qtile * QBLK) / KVBLK;
+  }
+
   // ---- staging via LDS-DMA (global_load_lds, probed: data lands at
   // lds_base + lane*16 with per-lane global sources — tools/gldsprobe.hip):
   // no staging registers, no ds_write pass, no vmcnt park.  The per-lane
@@ -182,12 +207,14 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     }
   };
 
-  stage_kv(0, 0);
+  // the first tile visited lands in buffer 0 whatever its parity: the
+  // buffer index counts from t0, not from tile 0
+  stage_kv(t0 * KVBLK, 0);
   __syncthreads();
 
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = t0; t < ntiles; ++t) {
     const int kv0 = t * KVBLK;
-    const int buf = t & 1;
+    const int buf = (t - t0) & 1;
     // stage next tile into the other buffer (global loads issue before the
     // MFMA stream — T14 spirit; ds_writes don't touch the compute buffer)
     if (t + 1 < ntiles) stage_kv((t + 1) * KVBLK, buf ^ 1);
@@ -237,15 +264,17 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
 #pragma unroll
     for (int nq = 0; nq < 2; ++nq) {
       const int qrow = rowb[nq] + l15;
-      const bool need_mask =
-          (kv0 + KVBLK - 1) > rowb[nq] || kv_end < kv0 + KVBLK;
+      const bool need_mask = (kv0 + KVBLK - 1) > rowb[nq] ||
+                             kv_end < kv0 + KVBLK ||
+                             (DOC && dsmax[nq] > kv0);
       if (need_mask) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             int key = kv0 + ckey[mt] + r;
-            if (key > qrow || key >= S) sfrag[mt][nq][r] = -INFINITY;
+            if (key > qrow || key >= S || (DOC && key < dstart[nq]))
+              sfrag[mt][nq][r] = -INFINITY;
           }
       }
       float tmax = -INFINITY;
@@ -333,8 +362,21 @@ void attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
                      float scale, hipStream_t stream) {
   int ntiles = (S + QBLK - 1) / QBLK;
   int64_t grid = (int64_t)B * Hq * ntiles;
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3((uint32_t)grid), dim3(256), 0,
-                     stream, (const short*)q, (const short*)k, (const short*)v,
-                     (short*)o, lse, B, S, Hq, Hkv, D, scale);
+  hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3((uint32_t)grid), dim3(256),
+                     0, stream, (const short*)q, (const short*)k,
+                     (const short*)v, (short*)o, lse, B, S, Hq, Hkv, D, scale,
+                     (const int*)nullptr);
+}
+
+void attn_fwd_doc_launch(const void* q, const void* k, const void* v, void* o,
+                         float* lse, const int* doc_start, int B, int S,
+                         int Hq, int Hkv, int D, float scale,
+                         hipStream_t stream) {
+  int ntiles = (S + QBLK - 1) / QBLK;
+  int64_t grid = (int64_t)B * Hq * ntiles;
+  hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((uint32_t)grid), dim3(256),
+                     0, stream, (const short*)q, (const short*)k,
+                     (const short*)v, (short*)o, lse, B, S, Hq, Hkv, D, scale,
+                     doc_start);
 }
 }

@@ -446,6 +446,66 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
   return {dq, dk, dv};
 }
 
+// document-masked variants: doc_start / doc_end are the [B,S] int32 tables
+// of ops/doc_mask.py (their contents are the caller's contract; the
+// kernels only keep a bad table from moving loads out of bounds)
+#define CHECK_DOC_TABLE(t, q)                                              \
+  TORCH_CHECK((t).is_cuda() && (t).device() == (q).device(),               \
+              #t " must be on q's device");                                \
+  TORCH_CHECK((t).dtype() == torch::kInt, #t " must be int32");            \
+  TORCH_CHECK((t).is_contiguous(), #t " must be contiguous");              \
+  TORCH_CHECK((t).dim() == 2 && (t).size(0) == (q).size(0) &&              \
+              (t).size(1) == (q).size(1), #t " must be [B,S]")
+
+std::vector<torch::Tensor> attn_fwd_doc(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v,
+                                        torch::Tensor doc_start,
+                                        double scale) {
+  CHECK_BF16_CONTIG(q);
+  CHECK_BF16_CONTIG(k);
+  CHECK_BF16_CONTIG(v);
+  TORCH_CHECK(q.dim() == 4, "q must be [B,S,Hq,D]");
+  CHECK_DOC_TABLE(doc_start, q);
+  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
+            D = (int)q.size(3);
+  const int Hkv = (int)k.size(2);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({(int64_t)B, (int64_t)Hq, (int64_t)S},
+                          q.options().dtype(torch::kFloat));
+  attn_fwd_doc_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                      lse.data_ptr<float>(), doc_start.data_ptr<int>(), B, S,
+                      Hq, Hkv, D, (float)scale, cur_stream());
+  return {o, lse};
+}
+
+std::vector<torch::Tensor> attn_bwd_doc(torch::Tensor dout, torch::Tensor q,
+                                        torch::Tensor k, torch::Tensor v,
+                                        torch::Tensor o, torch::Tensor lse,
+                                        torch::Tensor doc_start,
+                                        torch::Tensor doc_end, double scale) {
+  CHECK_BF16_CONTIG(dout);
+  TORCH_CHECK(q.dim() == 4, "q must be [B,S,Hq,D]");
+  CHECK_DOC_TABLE(doc_start, q);
+  CHECK_DOC_TABLE(doc_end, q);
+  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
+            D = (int)q.size(3);
+  const int Hkv = (int)k.size(2);
+  auto dq = torch::empty_like(q);
+  auto dk = torch::empty_like(k);
+  auto dv = torch::empty_like(v);
+  auto delta = torch::empty({(int64_t)B, (int64_t)Hq, (int64_t)S},
+                            q.options().dtype(torch::kFloat));
+  attn_bwd_doc_launch(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
+                      v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                      delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+                      dv.data_ptr(), doc_start.data_ptr<int>(),
+                      doc_end.data_ptr<int>(), B, S, Hq, Hkv, D, (float)scale,
+                      cur_stream());
+  return {dq, dk, dv};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -476,4 +536,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_scale_", &grad_scale_);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_fwd_doc", &attn_fwd_doc);
+  m.def("attn_bwd_doc", &attn_bwd_doc);
 }

@@ -109,4 +109,16 @@ void attn_bwd_launch(const void* dout, const void* q, const void* k,
                      const void* v, const void* o, const float* lse,
                      float* delta, void* dq, void* dk, void* dv, int B, int S,
                      int Hq, int Hkv, int D, float scale, hipStream_t stream);
+// document-masked mode for packed rows: doc_start/doc_end are [B,S] int32
+// (first token / exclusive end of each token's document)
+void attn_fwd_doc_launch(const void* q, const void* k, const void* v, void* o,
+                         float* lse, const int* doc_start, int B, int S,
+                         int Hq, int Hkv, int D, float scale,
+                         hipStream_t stream);
+void attn_bwd_doc_launch(const void* dout, const void* q, const void* k,
+                         const void* v, const void* o, const float* lse,
+                         float* delta, void* dq, void* dk, void* dv,
+                         const int* doc_start, const int* doc_end, int B,
+                         int S, int Hq, int Hkv, int D, float scale,
+                         hipStream_t stream);
 }

@@ -18,6 +18,8 @@ import logging
 import torch
 from torch.utils.data import Dataset
 
+from ..ops.doc_mask import doc_start_from_ids
+
 LOGGER = logging.getLogger(__name__)
 
 
@@ -31,17 +33,29 @@ def load_and_preprocess_data(args, config):
             seq_length=args.seq_length,
             num_samples=getattr(args, "num_samples", 4096),
             seed=args.seed,
+            doc_len=getattr(args, "synthetic_doc_len", 0),
+            doc_mask=getattr(args, "doc_mask", False),
         )
     return _load_hf_dataset(args, config)
 
 
 class PackedTokenDataset(Dataset):
     """Fixed-length rows over one flat token stream (int32 on host; rows
-    come out int64 as the CE kernel expects)."""
+    come out int64 as the CE kernel expects).
 
-    def __init__(self, stream: torch.Tensor, seq_length: int):
+    With doc_mask, rows carry an extra "doc_start" int32 [S]
+    (ops/doc_mask.py), computed on the host from the row's own tokens: a
+    document that began in the previous row counts from index 0 here."""
+
+    def __init__(self, stream: torch.Tensor, seq_length: int,
+                 eos_id: int | None = None, doc_mask: bool = False):
+        if doc_mask and eos_id is None:
+            raise ValueError("doc_mask needs the EOS id that separates the "
+                             "packed documents")
         self.stream = stream
         self.seq_length = seq_length
+        self.eos_id = eos_id
+        self.doc_mask = doc_mask
         self.n = stream.numel() // seq_length
 
     def __len__(self):
@@ -50,11 +64,14 @@ class PackedTokenDataset(Dataset):
     def __getitem__(self, idx):
         L = self.seq_length
         ids = self.stream[idx * L: (idx + 1) * L].long()
-        return {
+        row = {
             "input_ids": ids,
             "attention_mask": torch.ones(L, dtype=torch.long),
             "labels": ids.clone(),
         }
+        if self.doc_mask:
+            row["doc_start"] = doc_start_from_ids(ids[None], self.eos_id)[0]
+        return row
 
 
 def _load_hf_dataset(args, config):
@@ -84,6 +101,11 @@ def _load_hf_dataset(args, config):
     seq_length = min(seq_length, config.max_position_embeddings)
 
     eos = tokenizer.eos_token_id
+    doc_mask = getattr(args, "doc_mask", False)
+    if doc_mask and eos is None:
+        raise ValueError(
+            f"--doc-mask needs an EOS token to tell documents apart, and "
+            f"the tokenizer of {args.model_name} has none")
     pieces = []
     for row in tokenized["ids"]:
         pieces.append(np.asarray(row, dtype=np.int32))
@@ -94,4 +116,5 @@ def _load_hf_dataset(args, config):
     n_rows = stream.numel() // seq_length
     LOGGER.info(f"packed {stream.numel()} tokens into {n_rows} rows of "
                 f"{seq_length}")
-    return PackedTokenDataset(stream, seq_length)
+    return PackedTokenDataset(stream, seq_length, eos_id=eos,
+                              doc_mask=doc_mask)

@@ -128,7 +128,12 @@ class GPT2ForCausalLM(nn.Module):
                 tensor.normal_(0.0, std)
 
     def forward(self, input_ids, labels=None, attention_mask=None,
-                position_ids=None, **_):
+                position_ids=None, doc_start=None, **_):
+        if doc_start is not None:
+            raise NotImplementedError(
+                "GPT-2 does not support document-masked attention "
+                "(doc_start): its learned absolute positions would have to "
+                "be reset per document; use a Llama model or drop --doc-mask")
         B, S = input_ids.shape
         if position_ids is None:
             position_ids = torch.arange(S, device=input_ids.device)

@@ -20,8 +20,8 @@ from dataclasses import dataclass, field
 import torch
 import torch.nn as nn
 
-from ..ops import (RMSNorm, causal_lm_loss, flash_attention, qkv_rope,
-                   silu_mul)
+from ..ops import (RMSNorm, causal_lm_loss, doc_bounds, flash_attention,
+                   qkv_rope, silu_mul)
 from ..ops.embedding import Embedding
 from ..ops.fused_linear_ce import fused_causal_lm_loss
 from ..ops.rmsnorm import add_rmsnorm
@@ -86,7 +86,7 @@ class LlamaAttention(nn.Module):
         self.o_proj = nn.Linear(self.num_heads * d, h, bias=False,
                                 device=device, dtype=dtype)
 
-    def forward(self, x, position_ids=None):
+    def forward(self, x, position_ids=None, doc=None):
         B, S, _ = x.shape
         d = self.head_dim
         qkv = self.qkv_proj(x)
@@ -95,7 +95,7 @@ class LlamaAttention(nn.Module):
         q, k, v = qkv_rope(qkv, self.num_heads, self.num_kv_heads, d,
                            self.config.rope_theta, positions=position_ids,
                            max_pos=self.config.max_position_embeddings)
-        o = flash_attention(q, k, v)
+        o = flash_attention(q, k, v, doc=doc)
         return self.o_proj(o.reshape(B, S, self.num_heads * d))
 
 
@@ -123,21 +123,23 @@ class LlamaDecoderLayer(nn.Module):
             config.hidden_size, config.rms_norm_eps, device, dtype)
         self.mlp = LlamaMLP(config, device, dtype)
 
-    def forward(self, x, position_ids=None, residual=None):
+    def forward(self, x, position_ids=None, residual=None, doc=None):
         """Two call forms (both via __call__ so FSDP/checkpoint hooks fire):
         - forward(x): the reference chain x + attn(norm(x)) + mlp(...).
         - forward(delta, residual=res): fused (delta, residual) threading —
           each residual add is fused into the next RMSNorm kernel; returns
           (new_delta, new_residual), equivalent to forward(res + delta).
+        doc: the model's DocBounds (document-masked attention) or None.
         """
         if residual is None:
-            x = x + self.self_attn(self.input_layernorm(x), position_ids)
+            x = x + self.self_attn(self.input_layernorm(x), position_ids,
+                                   doc=doc)
             x = x + self.mlp(self.post_attention_layernorm(x))
             return x
         normed, residual = add_rmsnorm(residual, x,
                                        self.input_layernorm.weight,
                                        self.input_layernorm.eps)
-        a = self.self_attn(normed, position_ids)
+        a = self.self_attn(normed, position_ids, doc=doc)
         normed, residual = add_rmsnorm(residual, a,
                                        self.post_attention_layernorm.weight,
                                        self.post_attention_layernorm.eps)
@@ -192,11 +194,20 @@ class LlamaForCausalLM(nn.Module):
             m.reset_parameters()
 
     def forward(self, input_ids, labels=None, attention_mask=None,
-                position_ids=None, **_):
+                position_ids=None, doc_start=None, **_):
+        """doc_start (int32 [B,S], ops/doc_mask.py) confines attention to
+        each token's own document of a packed row; without it attention is
+        causal over the whole row.  Positions are NOT reset per document:
+        RoPE scores depend only on i - j, so attention inside a document is
+        the same whether its positions start at 0 or at its offset in the
+        row."""
         # attention_mask accepted for API parity (reference data pipeline
         # emits it, 01:69); attention is always causal over packed rows.
         if position_ids is not None and position_ids.dim() == 2:
             position_ids = position_ids[0]
+        # both mask tables once per forward; every layer (and every
+        # checkpoint recompute) gets this same object
+        doc = None if doc_start is None else doc_bounds(doc_start)
         x = self.embed_tokens(input_ids)
         if x.is_cuda:
             # fused (delta, residual) path: every residual add is fused
@@ -207,12 +218,12 @@ class LlamaForCausalLM(nn.Module):
             delta = torch.zeros_like(x)
             for layer in self.layers:
                 delta, residual = layer(delta, position_ids,
-                                        residual=residual)
+                                        residual=residual, doc=doc)
             x, _ = add_rmsnorm(residual, delta, self.norm.weight,
                                self.norm.eps)
         else:
             for layer in self.layers:
-                x = layer(x, position_ids)
+                x = layer(x, position_ids, doc=doc)
             x = self.norm(x)
         if labels is not None and x.is_cuda:
             # chunked fused projection+CE: the [B,S,V] logits (+grad) are

@@ -2,6 +2,8 @@
 from .adamw import FusedAdamW
 from .attention import flash_attention
 from .cross_entropy import causal_lm_loss, sharded_causal_lm_loss
+from .doc_mask import (DocBounds, doc_bounds, doc_start_from_ids,
+                       validate_doc_start)
 from .fused_linear_ce import fused_causal_lm_loss
 from .grad_clip import clip_grad_norm_, grad_sq_sum
 from .layernorm import LayerNorm, gelu
@@ -14,6 +16,10 @@ __all__ = [
     "flash_attention",
     "causal_lm_loss",
     "sharded_causal_lm_loss",
+    "DocBounds",
+    "doc_bounds",
+    "doc_start_from_ids",
+    "validate_doc_start",
     "fused_causal_lm_loss",
     "clip_grad_norm_",
     "grad_sq_sum",

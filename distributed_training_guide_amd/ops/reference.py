@@ -58,8 +58,13 @@ def silu_mul_ref(gu: torch.Tensor) -> torch.Tensor:
 
 
 def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                  scale: float) -> torch.Tensor:
-    """Causal GQA SDPA on [B, S, H, D] inputs, fp32 math."""
+                  scale: float,
+                  doc_start: torch.Tensor | None = None) -> torch.Tensor:
+    """Causal GQA SDPA on [B, S, H, D] inputs, fp32 math.  With doc_start
+    (int [B, S], ops/doc_mask.py) query i sees key j iff
+    doc_start[b, i] <= j <= i."""
+    if doc_start is not None:
+        return _attention_doc_ref(q, k, v, scale, doc_start)
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     group = Hq // Hkv
@@ -70,6 +75,23 @@ def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         kt = kt.repeat_interleave(group, dim=1)
         vt = vt.repeat_interleave(group, dim=1)
     o = F.scaled_dot_product_attention(qt, kt, vt, is_causal=True, scale=scale)
+    return o.permute(0, 2, 1, 3).to(q.dtype)
+
+
+def _attention_doc_ref(q, k, v, scale, doc_start):
+    B, S, Hq, D = q.shape
+    group = Hq // k.shape[2]
+    qt = q.permute(0, 2, 1, 3).float()
+    kt = k.permute(0, 2, 1, 3).float()
+    vt = v.permute(0, 2, 1, 3).float()
+    if group > 1:
+        kt = kt.repeat_interleave(group, dim=1)
+        vt = vt.repeat_interleave(group, dim=1)
+    j = torch.arange(S, device=q.device)
+    mask = (j.view(1, 1, S) <= j.view(1, S, 1)) & \
+        (j.view(1, 1, S) >= doc_start.long().view(B, S, 1))
+    o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask.unsqueeze(1),
+                                       scale=scale)
     return o.permute(0, 2, 1, 3).to(q.dtype)
 
 

@@ -27,7 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..models.llama import CausalLMOutput, LlamaConfig
-from ..ops import RMSNorm, flash_attention, rope, silu_mul
+from ..ops import RMSNorm, doc_bounds, flash_attention, rope, silu_mul
 from ..ops.cross_entropy import causal_lm_loss, sharded_causal_lm_loss
 
 LOGGER = logging.getLogger(__name__)
@@ -258,7 +258,7 @@ class TPLlamaAttention(nn.Module):
         self.o_proj = RowwiseLinear(config.num_attention_heads * d, h, mesh,
                                     device=device, dtype=dtype)
 
-    def forward(self, x, position_ids=None):
+    def forward(self, x, position_ids=None, doc=None):
         B, S, _ = x.shape  # x is REPLICATED (post seq-gather), full S
         d = self.head_dim
         qkv = self.qkv_proj(x)
@@ -271,7 +271,8 @@ class TPLlamaAttention(nn.Module):
         maxp = self.config.max_position_embeddings
         q = rope(q, theta, positions=position_ids, max_pos=maxp)
         k = rope(k, theta, positions=position_ids, max_pos=maxp)
-        o = flash_attention(q, k, v)
+        # full sequence, local heads: the [B,S] document tables apply as is
+        o = flash_attention(q, k, v, doc=doc)
         return self.o_proj(o.reshape(B, S, self.num_heads * d))
 
 
@@ -298,11 +299,12 @@ class TPLlamaDecoderLayer(nn.Module):
             config.hidden_size, config.rms_norm_eps, device, dtype)
         self.mlp = TPLlamaMLP(config, mesh, device, dtype)
 
-    def forward(self, x, position_ids=None):
+    def forward(self, x, position_ids=None, doc=None):
         # x: [B, S/tp, h] sequence-sharded
         g = self.mesh.tp_group
         h = gather_seq(self.input_layernorm(x), g)          # AG (06:90-95)
-        x = x + reduce_scatter_seq(self.self_attn(h, position_ids), g)  # RS
+        x = x + reduce_scatter_seq(
+            self.self_attn(h, position_ids, doc=doc), g)    # RS
         h = gather_seq(self.post_attention_layernorm(x), g)  # AG (06:102-105)
         x = x + reduce_scatter_seq(self.mlp(h), g)           # RS (06:108)
         return x
@@ -391,13 +393,16 @@ class TPLlamaForCausalLM(nn.Module):
         return [(sharded, group), (repl, None)]
 
     def forward(self, input_ids, labels=None, attention_mask=None,
-                position_ids=None, **_):
+                position_ids=None, doc_start=None, **_):
+        """doc_start: document-masked attention, as in
+        LlamaForCausalLM.forward (positions are not reset per document)."""
         g = self.mesh.tp_group
         if position_ids is not None and position_ids.dim() == 2:
             position_ids = position_ids[0]
+        doc = None if doc_start is None else doc_bounds(doc_start)
         x = reduce_scatter_seq(self.embed_tokens(input_ids), g)
         for layer in self.layers:
-            x = layer(x, position_ids)
+            x = layer(x, position_ids, doc=doc)
         x = gather_seq(self.norm(x), g)
         logits_local = self.lm_head(x)
         loss = None

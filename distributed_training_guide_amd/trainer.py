@@ -55,6 +55,14 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
         p.add_argument("--max-grad-norm", default=0.0, type=float,
                        help="clip the global gradient norm to this value, "
                             "fused into the AdamW update (0 = off)")
+        p.add_argument("--doc-mask", action="store_true",
+                       help="confine attention to each token's own document "
+                            "of a packed row (rows carry doc_start; Llama "
+                            "models only)")
+        p.add_argument("--synthetic-doc-len", default=0, type=int,
+                       help="synthetic dataset: write an EOS id at random "
+                            "gaps of this mean length (0 = one document "
+                            "per row)")
         p.add_argument("--deterministic", action="store_true")
         p.add_argument("--wandb", action="store_true")
         p.add_argument("--wandb-mode", default="rank0",
