@@ -40,9 +40,10 @@ __device__ __forceinline__ f32x4 mfma16b(bf16x8 a, bf16x8 b, f32x4 c) {
 // one row per 16-lane group (16 lanes x 8 bf16 = 128 elems = a whole
 // D=128 row per pass) — a row-per-wave version left 48/64 lanes idle at
 // D<=128 (guide §5 mistake 6)
+template <int D>
 __global__ void __launch_bounds__(256) attn_delta_kernel(
     const short* __restrict__ dout, const short* __restrict__ o,
-    float* __restrict__ delta, int B, int S, int Hq, int D) {
+    float* __restrict__ delta, int B, int S, int Hq) {
   const int grp = threadIdx.x >> 4;       // 16 groups per block
   const int gl = threadIdx.x & 15;
   int64_t nrows = (int64_t)B * S * Hq;
@@ -51,6 +52,7 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(
     const short* dp = dout + row * D;
     const short* op = o + row * D;
     float s = 0.f;
+#pragma unroll
     for (int i = gl * 8; i < D; i += 16 * 8) {
       bf16x8 dv = *reinterpret_cast<const bf16x8*>(dp + i);
       bf16x8 ov = *reinterpret_cast<const bf16x8*>(op + i);
@@ -78,21 +80,30 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(
 // j <= i < doc_end[b,j]); dq owns q rows and reads doc_start like the
 // forward.  DOC=false is the plain causal kernel (table unused, may be
 // null).
-template <bool DOC>
+//
+// The head dim D is a template parameter (64 or 128) so that every loop
+// over d-chunks has a compile-time bound (see attention_fwd.hip).  The
+// per-score arithmetic is one fma + raw v_exp_f32 for P and one fma + mul
+// for dS: scale*log2(e) is folded into the fma's multiplier, lse arrives
+// pre-multiplied by log2(e) and delta by scale (once per row, when they
+// are staged), and the causal/document mask touches only the tiles that
+// need one (exp2(-inf) = 0).
+template <int D, bool DOC>
 __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
     const short* __restrict__ dout, const short* __restrict__ q,
     const short* __restrict__ k, const short* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
     short* __restrict__ dk, short* __restrict__ dv, int B, int S, int Hq,
-    int Hkv, int D, float scale, const int* __restrict__ doc_end) {
+    int Hkv, float scale, const int* __restrict__ doc_end) {
+  static_assert(D == 64 || D == 128, "head dim must be 64 or 128");
   // double-buffered ROW-major staging of the 64-q-row tile (q[qrow][d],
   // dO[qrow][d], st_idx subtile image): serves BOTH the Q/dO A-fragments
   // (b128 row reads, replacing per-tile global gathers) and the
   // dV/dK B-fragments (tr16 hardware-transpose reads); plus lse/delta rows
-  __shared__ short q_lds[2][64 * 128];
-  __shared__ short do_lds[2][64 * 128];
-  __shared__ float lse_lds[2][64];
-  __shared__ float del_lds[2][64];
+  __shared__ short q_lds[2][64 * D];
+  __shared__ short do_lds[2][64 * D];
+  __shared__ __attribute__((aligned(16))) float lse_lds[2][64];
+  __shared__ __attribute__((aligned(16))) float del_lds[2][64];
 
   const int nkt = (S + 63) / 64;
   const int group = Hq / Hkv;
@@ -122,32 +133,32 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
   const int lg = lane >> 4;
 
   const int kv0 = kt * 64 + wid * 16;  // this wave's 16 keys
-  const int nd16 = D >> 4, nkc = D >> 5;
+  constexpr int nd16 = D >> 4, nkc = D >> 5;
+  const float c2 = scale * LOG2E;
   const int64_t strideS_q = (int64_t)Hq * D;
   const int64_t strideS_kv = (int64_t)Hkv * D;
   const short* kb = k + ((int64_t)b * S * Hkv + hkv) * D;
   const short* vb = v + ((int64_t)b * S * Hkv + hkv) * D;
 
   // K/V B-fragments (n = key l15, k = d lg*8+j — contiguous 16 B loads)
-  bf16x8 kf[4], vf[4];
+  bf16x8 kf[nkc], vf[nkc];
   {
     int key = kv0 + l15;
     int keyc = key < S ? key : S - 1;
     const short* kp = kb + (int64_t)keyc * strideS_kv + lg * 8;
     const short* vp = vb + (int64_t)keyc * strideS_kv + lg * 8;
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (c < nkc) {
-        kf[c] = *reinterpret_cast<const bf16x8*>(kp + c * 32);
-        vf[c] = *reinterpret_cast<const bf16x8*>(vp + c * 32);
-      }
+    for (int c = 0; c < nkc; ++c) {
+      kf[c] = *reinterpret_cast<const bf16x8*>(kp + c * 32);
+      vf[c] = *reinterpret_cast<const bf16x8*>(vp + c * 32);
+    }
   }
 
   // dK/dV accumulators: C[m=key][n=d] frags per d-tile
   // (lane: d = l15, key = kv0 + lg*4 + r)
-  f32x4 dkacc[8], dvacc[8];
+  f32x4 dkacc[nd16], dvacc[nd16];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < nd16; ++i) {
     dkacc[i] = {0.f, 0.f, 0.f, 0.f};
     dvacc[i] = {0.f, 0.f, 0.f, 0.f};
   }
@@ -179,8 +190,8 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
   // (h, q-tile)'s Q/dO tiles stream into the other buffer with no staging
   // registers and no vmcnt park; the per-lane global slot is pre-XOR'd so
   // the contiguous landing equals the st_idx subtile image.
-  const int nslot = D >> 3;
-  const int ncw = nslot >> 2;
+  constexpr int nslot = D >> 3;
+  constexpr int ncw = nslot >> 2;
   const int srow_half = lane >> 1;       // subtile-half row within chunk
   const int scol_half = (lane & 1) * 8;  // 8-col half within subtile
   auto stage_qdo = [&](int it, int buf) {
@@ -189,8 +200,7 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
     const short* qbse = q + ((int64_t)b * S * Hq + hh) * D;
     const short* dbse = dout + ((int64_t)b * S * Hq + hh) * D;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (i >= ncw) break;
+    for (int i = 0; i < ncw; ++i) {
       const int ch = wid * ncw + i;
       const int row = (ch & 1) * 32 + srow_half;
       int r = qt + row;
@@ -211,17 +221,18 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
           16, 0, 0);
     }
   };
+  // lse lands pre-multiplied by log2(e), delta by scale
   auto stage_lse = [&](int it, int buf) {
     const int hh = hkv * group + it / nqt;
     const int qt = qstart + (it % nqt) * 64;
     if (tid < 64) {
       const float* lseb = lse + ((int64_t)b * Hq + hh) * S;
       int rr = qt + tid < S ? qt + tid : S - 1;
-      lse_lds[buf][tid] = lseb[rr];
+      lse_lds[buf][tid] = lseb[rr] * LOG2E;
     } else if (tid < 128) {
       const float* delb = delta + ((int64_t)b * Hq + hh) * S;
       int rr = qt + tid - 64 < S ? qt + tid - 64 : S - 1;
-      del_lds[buf][tid - 64] = delb[rr];
+      del_lds[buf][tid - 64] = delb[rr] * scale;
     }
   };
 
@@ -242,7 +253,7 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
 
     // ---- per mt: S/dP MFMAs (C[m=qrow(perm)][n=key]; A = Q/dO rows in
     // perm16 order from LDS, B = kf/vf), then immediately
-    // P = exp(scale*S - lse), dS = scale*P*(dP - delta), packed into
+    // P = exp2(c2*S - lse'), dS = P*(scale*dP - delta'), packed into
     // A-operand order — only one mt of S/dP state stays live ----
     const int key = kv0 + l15;  // this lane's key (C n-position)
     // DOC also masks on every tile that reaches the end of the document
@@ -259,38 +270,47 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
       f32x4 sa0 = {0.f, 0.f, 0.f, 0.f}, da0 = {0.f, 0.f, 0.f, 0.f};
       f32x4 sa1 = {0.f, 0.f, 0.f, 0.f}, da1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < nkc) {
-          bf16x8 qa0 = *reinterpret_cast<const bf16x8*>(
-              ql + st_idx(qra, c * 32 + lg * 8));
-          bf16x8 qa1 = *reinterpret_cast<const bf16x8*>(
-              ql + st_idx(qrb, c * 32 + lg * 8));
-          bf16x8 do0 = *reinterpret_cast<const bf16x8*>(
-              dol + st_idx(qra, c * 32 + lg * 8));
-          bf16x8 do1 = *reinterpret_cast<const bf16x8*>(
-              dol + st_idx(qrb, c * 32 + lg * 8));
-          sa0 = mfma16b(qa0, kf[c], sa0);
-          sa1 = mfma16b(qa1, kf[c], sa1);
-          da0 = mfma16b(do0, vf[c], da0);
-          da1 = mfma16b(do1, vf[c], da1);
-        }
+      for (int c = 0; c < nkc; ++c) {
+        bf16x8 qa0 = *reinterpret_cast<const bf16x8*>(
+            ql + st_idx(qra, c * 32 + lg * 8));
+        bf16x8 qa1 = *reinterpret_cast<const bf16x8*>(
+            ql + st_idx(qrb, c * 32 + lg * 8));
+        bf16x8 do0 = *reinterpret_cast<const bf16x8*>(
+            dol + st_idx(qra, c * 32 + lg * 8));
+        bf16x8 do1 = *reinterpret_cast<const bf16x8*>(
+            dol + st_idx(qrb, c * 32 + lg * 8));
+        sa0 = mfma16b(qa0, kf[c], sa0);
+        sa1 = mfma16b(qa1, kf[c], sa1);
+        da0 = mfma16b(do0, vf[c], da0);
+        da1 = mfma16b(do1, vf[c], da1);
+      }
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const int mt = 2 * mth + half;
         const f32x4 sa = half ? sa1 : sa0;
         const f32x4 da = half ? da1 : da0;
         const int qoff = cpos16(mt, lg);
-        float p[4], ds[4];
+        // qoff is a multiple of 4: one b128 read each
+        const f32x4 lse4 =
+            *reinterpret_cast<const f32x4*>(&lse_lds[buf][qoff]);
+        const f32x4 del4 =
+            *reinterpret_cast<const f32x4*>(&del_lds[buf][qoff]);
+        float e[4], p[4], ds[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          e[r] = __builtin_fmaf(sa[r], c2, -lse4[r]);
+        if (diag) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int qrow = qt + qoff + r;
+            if (key > qrow || qrow >= S || key >= S || (DOC && qrow >= dend))
+              e[r] = -INFINITY;
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int qloc = qoff + r;
-          const int qrow = qt + qloc;
-          float e = (scale * sa[r] - lse_lds[buf][qloc]) * LOG2E;
-          if (diag && (key > qrow || qrow >= S || key >= S ||
-                       (DOC && qrow >= dend)))
-            e = -INFINITY;
-          p[r] = exp2f(e);
-          ds[r] = scale * p[r] * (da[r] - del_lds[buf][qloc]);
+          p[r] = __builtin_amdgcn_exp2f(e[r]);
+          ds[r] = p[r] * __builtin_fmaf(da[r], scale, -del4[r]);
         }
         const int kc = mt >> 1, rp = (mt & 1) * 2;
         pk_p[kc][rp + 0] = cvt_pk_bf16(p[0], p[1]);
@@ -303,8 +323,7 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
     // ---- dV += P^T dO ; dK += dS^T Q (B operands via tr16 transpose
     // reads from the same row-major tiles) ----
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      if (dt >= nd16) break;
+    for (int dt = 0; dt < nd16; ++dt) {
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc) {
         bf16x8 dofr = tr16_frag_st(dol, kc * 32 + lg * 8, dt * 16, l15);
@@ -328,8 +347,7 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
     short* dkp = dk + ((int64_t)b * S * Hkv + (int64_t)keyw * Hkv + hkv) * D;
     short* dvp = dv + ((int64_t)b * S * Hkv + (int64_t)keyw * Hkv + hkv) * D;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      if (dt >= nd16) break;
+    for (int dt = 0; dt < nd16; ++dt) {
       dkp[dt * 16 + l15] = f2bf(dkacc[dt][r]);
       dvp[dt * 16 + l15] = f2bf(dvacc[dt][r]);
     }
@@ -337,18 +355,19 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
 }
 
 // ---------------- dq ----------------
-template <bool DOC>
+template <int D, bool DOC>
 __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
     const short* __restrict__ dout, const short* __restrict__ q,
     const short* __restrict__ k, const short* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
-    short* __restrict__ dq, int B, int S, int Hq, int Hkv, int D,
-    float scale, const int* __restrict__ doc_start) {
+    short* __restrict__ dq, int B, int S, int Hq, int Hkv, float scale,
+    const int* __restrict__ doc_start) {
+  static_assert(D == 64 || D == 128, "head dim must be 64 or 128");
   // double-buffered K and V tiles (st_idx subtile image): K serves
   // the S^T A-fragments (b128 row reads) AND the dQ B-fragments (tr16
   // transpose reads); V serves the dP^T A-fragments
-  __shared__ short k_lds[2][64 * 128];
-  __shared__ short v_lds[2][64 * 128];
+  __shared__ short k_lds[2][64 * D];
+  __shared__ short v_lds[2][64 * D];
 
   const int ntq = (S + 127) / 128;
   const int gqa = Hq / Hkv;
@@ -383,7 +402,8 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
   // block (rows w*16 and w*16+64) — causal activity is then uniform
   // across waves (no per-tile barrier idling); see attention_fwd.hip
   const int rowb[2] = {qtile * 128 + wid * 16, qtile * 128 + 64 + wid * 16};
-  const int nd16 = D >> 4, nkc = D >> 5;
+  constexpr int nd16 = D >> 4, nkc = D >> 5;
+  const float c2 = scale * LOG2E;
   const int64_t strideS_q = (int64_t)Hq * D;
   const int64_t strideS_kv = (int64_t)Hkv * D;
   const short* qb = q + ((int64_t)b * S * Hq + h) * D;
@@ -393,8 +413,9 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
   const float* lseb = lse + ((int64_t)b * Hq + h) * S;
   const float* delb = delta + ((int64_t)b * Hq + h) * S;
 
-  // Q / dO B-fragments (n = qrow = l15 per nq tile) + per-lane lse/delta
-  bf16x8 qf[2][4], dof[2][4];
+  // Q / dO B-fragments (n = qrow = l15 per nq tile) + per-lane lse/delta,
+  // lse pre-multiplied by log2(e) and delta by scale
+  bf16x8 qf[2][nkc], dof[2][nkc];
   float lse_r[2], del_r[2];
 #pragma unroll
   for (int nq = 0; nq < 2; ++nq) {
@@ -403,19 +424,18 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
     const short* qp = qb + (int64_t)qrc * strideS_q + lg * 8;
     const short* dop = dob + (int64_t)qrc * strideS_q + lg * 8;
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (c < nkc) {
-        qf[nq][c] = *reinterpret_cast<const bf16x8*>(qp + c * 32);
-        dof[nq][c] = *reinterpret_cast<const bf16x8*>(dop + c * 32);
-      }
-    lse_r[nq] = lseb[qrc];
-    del_r[nq] = delb[qrc];
+    for (int c = 0; c < nkc; ++c) {
+      qf[nq][c] = *reinterpret_cast<const bf16x8*>(qp + c * 32);
+      dof[nq][c] = *reinterpret_cast<const bf16x8*>(dop + c * 32);
+    }
+    lse_r[nq] = lseb[qrc] * LOG2E;
+    del_r[nq] = delb[qrc] * scale;
   }
 
   // dQ accumulators: C[m=qrow][n=d] frags (lane: d = l15, qrow = lg*4+r)
-  f32x4 dqacc[8][2];
+  f32x4 dqacc[nd16][2];
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt)
+  for (int dt = 0; dt < nd16; ++dt)
 #pragma unroll
     for (int nq = 0; nq < 2; ++nq) dqacc[dt][nq] = {0.f, 0.f, 0.f, 0.f};
 
@@ -438,14 +458,13 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
   }
 
   // LDS-DMA staging (global_load_lds; see attention_fwd.hip)
-  const int nslot = D >> 3;
-  const int ncw = nslot >> 2;
+  constexpr int nslot = D >> 3;
+  constexpr int ncw = nslot >> 2;
   const int srow_half = lane >> 1;       // subtile-half row within chunk
   const int scol_half = (lane & 1) * 8;  // 8-col half within subtile
   auto stage_k = [&](int kv0s, int buf) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (i >= ncw) break;
+    for (int i = 0; i < ncw; ++i) {
       const int ch = wid * ncw + i;
       const int key = (ch & 1) * 32 + srow_half;
       int kg = kv0s + key;
@@ -497,17 +516,16 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
         f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (c < nkc) {
-            bf16x8 ka = *reinterpret_cast<const bf16x8*>(
-                kl + st_idx(kr, c * 32 + lg * 8));
-            bf16x8 va = *reinterpret_cast<const bf16x8*>(
-                vl + st_idx(kr, c * 32 + lg * 8));
-            s0 = mfma16b(ka, qf[0][c], s0);
-            d0 = mfma16b(va, dof[0][c], d0);
-            s1 = mfma16b(ka, qf[1][c], s1);
-            d1 = mfma16b(va, dof[1][c], d1);
-          }
+        for (int c = 0; c < nkc; ++c) {
+          bf16x8 ka = *reinterpret_cast<const bf16x8*>(
+              kl + st_idx(kr, c * 32 + lg * 8));
+          bf16x8 va = *reinterpret_cast<const bf16x8*>(
+              vl + st_idx(kr, c * 32 + lg * 8));
+          s0 = mfma16b(ka, qf[0][c], s0);
+          d0 = mfma16b(va, dof[0][c], d0);
+          s1 = mfma16b(ka, qf[1][c], s1);
+          d1 = mfma16b(va, dof[1][c], d1);
+        }
         const int koff = cpos16(mt, lg);
         const int kc = mt >> 1, rp = (mt & 1) * 2;
 #pragma unroll
@@ -517,17 +535,25 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
                             (DOC && dsmax[nq] > kv0);
           const f32x4 sv = nq ? s1 : s0;
           const f32x4 dv = nq ? d1 : d0;
-          float ds[4];
+          // P = exp2(c2*S - lse'), dS = P*(scale*dP - delta'); the mask
+          // touches only the tiles that need one (exp2(-inf) = 0)
+          float e[4], ds[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int keyr = kv0 + koff + r;
-            float e = (scale * sv[r] - lse_r[nq]) * LOG2E;
-            if (diag && (keyr > qrow || keyr >= S || qrow >= S ||
-                         (DOC && keyr < dstart[nq])))
-              e = -INFINITY;
-            float p = exp2f(e);
-            ds[r] = scale * p * (dv[r] - del_r[nq]);
+          for (int r = 0; r < 4; ++r)
+            e[r] = __builtin_fmaf(sv[r], c2, -lse_r[nq]);
+          if (diag) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int keyr = kv0 + koff + r;
+              if (keyr > qrow || keyr >= S || qrow >= S ||
+                  (DOC && keyr < dstart[nq]))
+                e[r] = -INFINITY;
+            }
           }
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            ds[r] = __builtin_amdgcn_exp2f(e[r]) *
+                    __builtin_fmaf(dv[r], scale, -del_r[nq]);
           pk_ds[nq][kc][rp + 0] = cvt_pk_bf16(ds[0], ds[1]);
           pk_ds[nq][kc][rp + 1] = cvt_pk_bf16(ds[2], ds[3]);
         }
@@ -536,8 +562,7 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
       // ---- dQ += dS K: B operand [k=key][n=d] via tr16 transpose reads
       // from the row-major K tile ----
 #pragma unroll
-      for (int dt = 0; dt < 8; ++dt) {
-        if (dt >= nd16) break;
+      for (int dt = 0; dt < nd16; ++dt) {
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
 #ifdef DQ_SCALAR_B
@@ -568,8 +593,7 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
       if (qrow >= S) continue;
       short* dqp = dq + ((int64_t)b * S * Hq + (int64_t)qrow * Hq + h) * D;
 #pragma unroll
-      for (int dt = 0; dt < 8; ++dt) {
-        if (dt >= nd16) break;
+      for (int dt = 0; dt < nd16; ++dt) {
         dqp[dt * 16 + l15] = f2bf(dqacc[dt][nq][r]);
       }
     }
@@ -586,20 +610,24 @@ void bwd_launch(const void* dout, const void* q, const void* k, const void* v,
   int64_t nrows = (int64_t)B * S * Hq;
   int64_t dwant = (nrows + 15) / 16;
   int dgrid = (int)(dwant < 2048 ? (dwant < 1 ? 1 : dwant) : 2048);
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, stream,
-                     (const short*)dout, (const short*)o, delta, B, S, Hq, D);
+  // bindings.cpp admits D of 64 or 128 only
+  const bool d64 = D == 64;
+  hipLaunchKernelGGL(d64 ? attn_delta_kernel<64> : attn_delta_kernel<128>,
+                     dim3(dgrid), dim3(256), 0, stream, (const short*)dout,
+                     (const short*)o, delta, B, S, Hq);
   int nkt = (S + 63) / 64;
-  hipLaunchKernelGGL(attn_dkdv_kernel<DOC>,
-                     dim3((uint32_t)((int64_t)B * Hkv * nkt)), dim3(256), 0,
-                     stream, (const short*)dout, (const short*)q,
-                     (const short*)k, (const short*)v, lse, delta, (short*)dk,
-                     (short*)dv, B, S, Hq, Hkv, D, scale, doc_end);
+  auto dkdv = d64 ? attn_dkdv_kernel<64, DOC> : attn_dkdv_kernel<128, DOC>;
+  hipLaunchKernelGGL(dkdv, dim3((uint32_t)((int64_t)B * Hkv * nkt)),
+                     dim3(256), 0, stream, (const short*)dout,
+                     (const short*)q, (const short*)k, (const short*)v, lse,
+                     delta, (short*)dk, (short*)dv, B, S, Hq, Hkv, scale,
+                     doc_end);
   int ntq = (S + 127) / 128;
-  hipLaunchKernelGGL(attn_dq_kernel<DOC>,
-                     dim3((uint32_t)((int64_t)B * Hq * ntq)), dim3(256), 0,
+  auto dqk = d64 ? attn_dq_kernel<64, DOC> : attn_dq_kernel<128, DOC>;
+  hipLaunchKernelGGL(dqk, dim3((uint32_t)((int64_t)B * Hq * ntq)), dim3(256), 0,
                      stream, (const short*)dout, (const short*)q,
                      (const short*)k, (const short*)v, lse, delta, (short*)dq,
-                     B, S, Hq, Hkv, D, scale, doc_start);
+                     B, S, Hq, Hkv, scale, doc_start);
 }
 }  // namespace
 

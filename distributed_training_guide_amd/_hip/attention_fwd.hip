@@ -58,16 +58,22 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
 // holds, per token, the index of the first token of its document; query i
 // sees key j iff doc_start[b,i] <= j <= i.  DOC=false is the plain causal
 // kernel (doc_start unused, may be null).
-template <bool DOC>
+//
+// The head dim D is a template parameter (64 or 128): with a run-time D
+// every kc/dt step of the tile loop carried its own `if (kc < nkc)` branch,
+// which split the MFMA stream into one basic block per step (a full LDS
+// wait before every 4 MFMAs, no hoisting of operand reads across steps).
+template <int D, bool DOC>
 __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, short* __restrict__ o,
-    float* __restrict__ lse_out, int B, int S, int Hq, int Hkv, int D,
-    float scale, const int* __restrict__ doc_start) {
+    float* __restrict__ lse_out, int B, int S, int Hq, int Hkv, float scale,
+    const int* __restrict__ doc_start) {
+  static_assert(D == 64 || D == 128, "head dim must be 64 or 128");
   // both tiles in the 16-col-subtile image (st_idx; conflict-free tr16
   // reads + b128 row reads), double-buffered
-  __shared__ short k_lds[2][KVBLK * 128];
-  __shared__ short v_lds[2][KVBLK * 128];
+  __shared__ short k_lds[2][KVBLK * D];
+  __shared__ short v_lds[2][KVBLK * D];
 
   const int ntq = (S + QBLK - 1) / QBLK;
   const int gqa = Hq / Hkv;
@@ -106,8 +112,8 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   // the q range, so causal tile-skipping is uniform across waves and no
   // wave idles at the per-tile barrier (guide: wave load balance)
   const int rowb[2] = {qtile * QBLK + wid * 16, qtile * QBLK + 64 + wid * 16};
-  const int nd16 = D >> 4;                 // 16-d tiles (8 for D=128)
-  const int nkc = D >> 5;                  // 32-d MFMA K chunks
+  constexpr int nd16 = D >> 4;             // 16-d tiles (8 for D=128)
+  constexpr int nkc = D >> 5;              // 32-d MFMA K chunks
   const int64_t strideS_q = (int64_t)Hq * D;
   const int64_t strideS_kv = (int64_t)Hkv * D;
   const short* qb = q + ((int64_t)b * S * Hq + h) * D;
@@ -115,16 +121,15 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   const short* vb = v + ((int64_t)b * S * Hkv + hkv) * D;
 
   // ---- Q B-fragments: [nq 2][kc], row q0 + nq*16 + l15, d = kc*32+lg*8 --
-  bf16x8 qf[2][4];
+  bf16x8 qf[2][nkc];
 #pragma unroll
   for (int nq = 0; nq < 2; ++nq) {
     int qrow = rowb[nq] + l15;
     if (qrow >= S) qrow = S - 1;
     const short* qp = qb + (int64_t)qrow * strideS_q + lg * 8;
 #pragma unroll
-    for (int kc = 0; kc < 4; ++kc)
-      if (kc < nkc)
-        qf[nq][kc] = *reinterpret_cast<const bf16x8*>(qp + kc * 32);
+    for (int kc = 0; kc < nkc; ++kc)
+      qf[nq][kc] = *reinterpret_cast<const bf16x8*>(qp + kc * 32);
   }
 
   // key permutation: C-fragment m-position p (= mt*16 + lg*4 + r) must hold
@@ -143,12 +148,15 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     ckey[mt] = (mt >> 1) * 32 + lg * 8 + (mt & 1) * 4;
 
   // O^T accumulators: [d tile][nq] C frags; lane: qrow=l15, d=lg*4+r
-  f32x4 oacc[8][2];
+  f32x4 oacc[nd16][2];
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt)
+  for (int dt = 0; dt < nd16; ++dt)
 #pragma unroll
     for (int nq = 0; nq < 2; ++nq) oacc[dt][nq] = {0.f, 0.f, 0.f, 0.f};
+  // running row max, raw (for lse) and pre-multiplied by scale*log2(e)
+  // (the exponent offset of everything accumulated so far)
   float mrow[2] = {-INFINITY, -INFINITY};
+  float mcrow[2] = {-INFINITY, -INFINITY};
   float lrow[2] = {0.f, 0.f};
 
   const int kv_end = min(S, qtile * QBLK + QBLK);
@@ -180,14 +188,13 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   // global slot is pre-XOR'd so the contiguous landing equals the
   // st_idx subtile image; tile t+1's DMA issues at the top of tile t and
   // completes under a full tile of MFMA before the end-of-tile barrier.
-  const int nslot = D >> 3;
-  const int ncw = nslot >> 2;     // chunks per wave per tensor
+  constexpr int nslot = D >> 3;
+  constexpr int ncw = nslot >> 2;  // chunks per wave per tensor
   const int srow_half = lane >> 1;       // subtile-half row within chunk
   const int scol_half = (lane & 1) * 8;  // 8-col half within subtile
   auto stage_kv = [&](int kv0, int buf) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (i >= ncw) break;
+    for (int i = 0; i < ncw; ++i) {
       const int ch = wid * ncw + i;
       const int key = (ch & 1) * 32 + srow_half;
       int kg = kv0 + key;
@@ -240,17 +247,16 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
       f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
       f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kc = 0; kc < 4; ++kc)
-        if (kc < nkc) {
-          bf16x8 kfa = *reinterpret_cast<const bf16x8*>(
-              kl + st_idx(kra, kc * 32 + lg * 8));
-          bf16x8 kfb = *reinterpret_cast<const bf16x8*>(
-              kl + st_idx(krb, kc * 32 + lg * 8));
-          a0 = mfma16(kfa, qf[0][kc], a0);
-          b0 = mfma16(kfb, qf[0][kc], b0);
-          a1 = mfma16(kfa, qf[1][kc], a1);
-          b1 = mfma16(kfb, qf[1][kc], b1);
-        }
+      for (int kc = 0; kc < nkc; ++kc) {
+        bf16x8 kfa = *reinterpret_cast<const bf16x8*>(
+            kl + st_idx(kra, kc * 32 + lg * 8));
+        bf16x8 kfb = *reinterpret_cast<const bf16x8*>(
+            kl + st_idx(krb, kc * 32 + lg * 8));
+        a0 = mfma16(kfa, qf[0][kc], a0);
+        b0 = mfma16(kfb, qf[0][kc], b0);
+        a1 = mfma16(kfa, qf[1][kc], a1);
+        b1 = mfma16(kfb, qf[1][kc], b1);
+      }
       sfrag[2 * mth][0] = a0;
       sfrag[2 * mth][1] = a1;
       sfrag[2 * mth + 1][0] = b0;
@@ -259,6 +265,11 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     __builtin_amdgcn_s_setprio(0);
 
     // ---- causal mask + online softmax (rows lane-local) ----
+    // p = exp2(s*c - m*c) as one fma and one raw v_exp_f32 per score.
+    // Masked scores are -inf (set only on tiles that need a mask) and
+    // exp2(-inf) = 0 without a per-score guard, provided the offset is
+    // finite: a row with no visible key yet has m = -inf, and takes a
+    // finite stand-in for m*c — once per row, not once per score.
     u32x4 pk[2][2];  // [nq][kc]: 4 regs of 2 bf16 (keys j=0..7)
     float alpha[2];
 #pragma unroll
@@ -286,10 +297,13 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
       // row spread over lanes l15, l15+16, l15+32, l15+48
       tmax = fmaxf(tmax, __shfl_xor(tmax, 16, WAVE));
       tmax = fmaxf(tmax, __shfl_xor(tmax, 32, WAVE));
-      float mnew = fmaxf(mrow[nq], tmax);
-      alpha[nq] =
-          (mrow[nq] == -INFINITY) ? 0.0f : exp2f((mrow[nq] - mnew) * c);
+      const float mnew = fmaxf(mrow[nq], tmax);
+      const float mcn = mnew * c;
+      const float mc = (mnew == -INFINITY) ? 0.0f : mcn;
+      // first visible tile of a row: mcrow = -inf gives alpha = 0
+      alpha[nq] = __builtin_amdgcn_exp2f(mcrow[nq] - mc);
       mrow[nq] = mnew;
+      mcrow[nq] = mcn;
       float psum = 0.f;
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
@@ -297,7 +311,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
         f32x4 p;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          p[r] = (s[r] == -INFINITY) ? 0.0f : exp2f((s[r] - mnew) * c);
+          p[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c, -mc));
           psum += p[r];
         }
         // keys of this C tile are already in B-operand order: mt -> (kc =
@@ -315,8 +329,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     const short* vt = v_lds[buf];
     __builtin_amdgcn_s_setprio(1);  // T5: prioritize the P.V MFMA stream
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      if (dt >= nd16) break;
+    for (int dt = 0; dt < nd16; ++dt) {
       bf16x8 va[2];
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc)
@@ -343,8 +356,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     const float invl = (lrow[nq] > 0.f) ? 1.0f / lrow[nq] : 0.0f;
     short* op = o + ((int64_t)b * S * Hq + (int64_t)qrow * Hq + h) * D;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      if (dt >= nd16) break;
+    for (int dt = 0; dt < nd16; ++dt) {
       s16x4v outv;
 #pragma unroll
       for (int r = 0; r < 4; ++r) outv[r] = f2bf(oacc[dt][nq][r] * invl);
@@ -356,27 +368,34 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   }
 }
 
+namespace {
+template <bool DOC>
+void fwd_launch(const void* q, const void* k, const void* v, void* o,
+                float* lse, const int* doc_start, int B, int S, int Hq,
+                int Hkv, int D, float scale, hipStream_t stream) {
+  int ntiles = (S + QBLK - 1) / QBLK;
+  int64_t grid = (int64_t)B * Hq * ntiles;
+  // bindings.cpp admits D of 64 or 128 only
+  auto kern = D == 64 ? attn_fwd_kernel<64, DOC> : attn_fwd_kernel<128, DOC>;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, stream,
+                     (const short*)q, (const short*)k, (const short*)v,
+                     (short*)o, lse, B, S, Hq, Hkv, scale, doc_start);
+}
+}  // namespace
+
 extern "C" {
 void attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
                      float* lse, int B, int S, int Hq, int Hkv, int D,
                      float scale, hipStream_t stream) {
-  int ntiles = (S + QBLK - 1) / QBLK;
-  int64_t grid = (int64_t)B * Hq * ntiles;
-  hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3((uint32_t)grid), dim3(256),
-                     0, stream, (const short*)q, (const short*)k,
-                     (const short*)v, (short*)o, lse, B, S, Hq, Hkv, D, scale,
-                     (const int*)nullptr);
+  fwd_launch<false>(q, k, v, o, lse, nullptr, B, S, Hq, Hkv, D, scale,
+                    stream);
 }
 
 void attn_fwd_doc_launch(const void* q, const void* k, const void* v, void* o,
                          float* lse, const int* doc_start, int B, int S,
                          int Hq, int Hkv, int D, float scale,
                          hipStream_t stream) {
-  int ntiles = (S + QBLK - 1) / QBLK;
-  int64_t grid = (int64_t)B * Hq * ntiles;
-  hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((uint32_t)grid), dim3(256),
-                     0, stream, (const short*)q, (const short*)k,
-                     (const short*)v, (short*)o, lse, B, S, Hq, Hkv, D, scale,
-                     doc_start);
+  fwd_launch<true>(q, k, v, o, lse, doc_start, B, S, Hq, Hkv, D, scale,
+                   stream);
 }
 }

@@ -116,7 +116,12 @@ __global__ void __launch_bounds__(256) add_rmsnorm_fwd_kernel(
 // RES adds the residual gradient dres (streamed in pass 2) to dx; the
 // fused op exists for H % 8 == 0 only, so only the plain instantiation
 // carries the scalar fallback.
-template <bool RES>
+// NCH is the number of 2048-column chunks a thread owns (H <= NCH * 2048):
+// pass 2 walks them by a COMPILE-TIME index. With a run-time chunk counter
+// the accumulator array is dynamically indexed and the compiler places it
+// in private (scratch) memory — a read-modify-write of scratch per element
+// that doubled the kernel's traffic.
+template <bool RES, int NCH>
 __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(
     const short* __restrict__ dy, const short* __restrict__ dres,
     const short* __restrict__ x, const short* __restrict__ w,
@@ -129,10 +134,9 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(
   const float invH = 1.0f / (float)H;
   const bool vec = RES || ((H & 7) == 0 && H <= 2048 * 8);
   // per-thread dw accumulators: chunk c covers column i = c*2048 + tid*8
-  const int nch = (H + 2047) / 2048;
-  float dwacc[8][8];
+  float dwacc[NCH][8];
 #pragma unroll
-  for (int c = 0; c < 8; ++c)
+  for (int c = 0; c < NCH; ++c)
 #pragma unroll
     for (int j = 0; j < 8; ++j) dwacc[c][j] = 0.0f;
 
@@ -163,26 +167,28 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(
     }
     dot = block4_sum(dot, scratch) * invH;
     if (vec) {
-      int c = 0;
-      for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8, ++c) {
-        s16x8 dv = *reinterpret_cast<const s16x8*>(dy_l + i);
-        s16x8 xv = *reinterpret_cast<const s16x8*>(x_l + i);
-        s16x8 wv = *reinterpret_cast<const s16x8*>(w + i);
-        s16x8 rv;
-        if constexpr (RES)
-          rv = *reinterpret_cast<const s16x8*>(drr + i);
-        s16x8 o;
-        float* acc = dwacc[c];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float g = bf2f(dv[j]) * bf2f(wv[j]);
-          float xhat = bf2f(xv[j]) * rs;
-          float d = rs * (g - xhat * dot);
-          if constexpr (RES) d += bf2f(rv[j]);
-          o[j] = f2bf(d);
-          acc[j] += bf2f(dv[j]) * xhat;
+      for (int c = 0; c < NCH; ++c) {
+        const int i = c * 2048 + threadIdx.x * 8;
+        if (i < H) {
+          s16x8 dv = *reinterpret_cast<const s16x8*>(dy_l + i);
+          s16x8 xv = *reinterpret_cast<const s16x8*>(x_l + i);
+          s16x8 wv = *reinterpret_cast<const s16x8*>(w + i);
+          s16x8 rv;
+          if constexpr (RES)
+            rv = *reinterpret_cast<const s16x8*>(drr + i);
+          s16x8 o;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float g = bf2f(dv[j]) * bf2f(wv[j]);
+            float xhat = bf2f(xv[j]) * rs;
+            float d = rs * (g - xhat * dot);
+            if constexpr (RES) d += bf2f(rv[j]);
+            o[j] = f2bf(d);
+            dwacc[c][j] += bf2f(dv[j]) * xhat;
+          }
+          *reinterpret_cast<s16x8*>(dxr + i) = o;
         }
-        *reinterpret_cast<s16x8*>(dxr + i) = o;
       }
     } else {
       // scalar fallback: accumulate straight to the partial row (rare)
@@ -200,8 +206,7 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(
   float* dwp = dw_partial + (int64_t)blockIdx.x * H;
   if (vec) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (c >= nch) break;
+    for (int c = 0; c < NCH; ++c) {
       int i = c * 2048 + threadIdx.x * 8;
       if (i < H) {
 #pragma unroll
@@ -211,20 +216,40 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(
   }
 }
 
+template <bool RES, int NCH>
+static void rmsnorm_bwd_nch(const void* dy, const void* dres, const void* x,
+                            const void* w, const void* rstd, void* dx,
+                            float* dw_partial, int nblocks, int64_t nrows,
+                            int H, hipStream_t s) {
+  size_t shmem = 2 * (size_t)H * sizeof(short);
+  hipLaunchKernelGGL((rmsnorm_bwd_kernel<RES, NCH>), dim3(nblocks), dim3(256),
+                     shmem, s, (const short*)dy, (const short*)dres,
+                     (const short*)x, (const short*)w, (const float*)rstd,
+                     (short*)dx, dw_partial, nrows, H);
+}
+
 template <bool RES>
 static void rmsnorm_bwd(const void* dy, const void* dres, const void* x,
                         const void* w, const void* rstd, void* dx,
                         float* dw_partial, void* dw, int nblocks,
                         int64_t nrows, int H, hipStream_t s) {
-  // scalar fallback (H not a multiple of 8) accumulates into dw_partial
-  // directly, so it must start zeroed; the vectorized path overwrites.
-  if (!RES && ((H & 7) || H > 2048 * 8))
-    hipMemsetAsync(dw_partial, 0, (size_t)nblocks * H * sizeof(float), s);
-  size_t shmem = 2 * (size_t)H * sizeof(short);
-  hipLaunchKernelGGL(rmsnorm_bwd_kernel<RES>, dim3(nblocks), dim3(256), shmem,
-                     s, (const short*)dy, (const short*)dres, (const short*)x,
-                     (const short*)w, (const float*)rstd, (short*)dx,
-                     dw_partial, nrows, H);
+  // scalar fallback (H not a multiple of 8, or past the 8 register chunks)
+  // accumulates into dw_partial directly, so it must start zeroed; the
+  // vectorized path overwrites. It keeps no register accumulators, so the
+  // one-chunk instantiation serves it.
+  const bool scalar = !RES && ((H & 7) || H > 2048 * 8);
+  if (scalar)
+    (void)hipMemsetAsync(dw_partial, 0, (size_t)nblocks * H * sizeof(float),
+                         s);
+  const int nch = scalar ? 1 : (H + 2047) / 2048;
+#define RMSNORM_BWD_NCH(N)                                                  \
+  rmsnorm_bwd_nch<RES, N>(dy, dres, x, w, rstd, dx, dw_partial, nblocks,    \
+                          nrows, H, s)
+  if (nch <= 1) RMSNORM_BWD_NCH(1);
+  else if (nch <= 2) RMSNORM_BWD_NCH(2);
+  else if (nch <= 4) RMSNORM_BWD_NCH(4);
+  else RMSNORM_BWD_NCH(8);
+#undef RMSNORM_BWD_NCH
   colsum_launch(dw_partial, dw, nblocks, H, s);
 }
 
