@@ -1,22 +1,26 @@
-// Causal flash-attention backward for gfx950 — v2: same idiom set as
-// attention_fwd.hip v3 (swapped/permuted MFMA fragments with in-register
-// P/dS, direct-from-L2 A/B operand loads, transposed double-buffered LDS
-// for the k-dim-transposed operands).
-// Counterpart of attention_fwd.hip; replaces flash-attn-2's backward
+// Causal flash-attention backward for gfx950, the counterpart of
+// attention_fwd.hip with the same idiom set: swapped / permuted MFMA
+// fragments with P and dS packed in registers, row-major st_idx tiles in
+// double-buffered LDS DMA-staged a tile ahead, read as b128 rows and through
+// the tr16 hardware transpose. Replaces flash-attn-2's backward
 // (SURVEY.md §2b "Flash attention 2", "bwd recompute variant").
 //
 // Standard flash-2 backward with lse recompute, split into three atomic-free
 // kernels (the loop order that would fuse them needs cross-block atomics on
 // dq — prohibitive write amplification at training shapes):
 //   1. delta[b,h,s] = rowsum(dO * O)
-//   2. dk/dv: block owns 64 keys of one (b, hkv) (one wave = 16 keys);
-//      loops (gqa-head, 64-q-row tile), accumulating dK/dV in registers.
-//      Q^T / dO^T tiles staged transposed+double-buffered in LDS; Q/dO
-//      A-fragments read straight from global (L2-resident with the
-//      XCD-aware remap); P^T/dS^T stay in registers via the perm16 trick.
-//   3. dq: block owns 128 q rows of one (b, hq) (one wave = 32); loops
-//      64-key tiles; the fwd-v3 structure with K^T staged transposed and
-//      dS packed in registers as the dQ MFMA's A operand.
+//   2. dk/dv: block owns 64 keys of one (b, hkv) (one wave = 16 keys, its
+//      K/V B-fragments loaded once from global); loops (gqa-head, 64-q-row
+//      tile), accumulating dK/dV in registers. The Q and dO tiles are staged
+//      row-major (stage_tile_pair) and serve both the S/dP MFMAs'
+//      A-fragments (b128 row reads in perm16 order) and the dV/dK MFMAs'
+//      B-fragments (tr16 transpose reads); P^T/dS^T stay in registers via
+//      the perm16 trick.
+//   3. dq: block owns 128 q rows of one (b, hq) (one wave = 32, its Q/dO
+//      B-fragments loaded once from global); loops 64-key tiles like the
+//      forward, with K and V staged row-major: K serves the S^T A-fragments
+//      (b128) and the dQ B-fragments (tr16), V the dP^T A-fragments; dS is
+//      packed in registers as the dQ MFMA's A operand.
 // Math (S_raw = Q.K^T, P = exp(scale*S_raw - lse)):
 //   dV += P^T dO
 //   dP = dO V^T;  dS_raw = scale * P * (dP - delta)
@@ -26,15 +30,8 @@
 //   A[m][k]: lane l -> m = l&15, k = (l>>4)*8 + j   (k spans 0..31)
 //   B[k][n]: lane l -> n = l&15, k = (l>>4)*8 + j
 //   C/D    : lane l -> n = l&15, m = (l>>4)*4 + r
-#include "common.h"
+#include "attention_common.h"
 #include "launchers.h"
-
-using bf16x8 = s16x8;
-#define LOG2E 1.4426950408889634f
-
-__device__ __forceinline__ f32x4 mfma16b(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 // ---------------- delta = rowsum(dO * O) ----------------
 // one row per 16-lane group (16 lanes x 8 bf16 = 128 elems = a whole
@@ -108,23 +105,10 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
   const int nkt = (S + 63) / 64;
   const int group = Hq / Hkv;
 
-  // XCD-aware remap: blocks of one (b,hkv) on one XCD (shared Q/dO/K/V L2)
-  int b, hkv, kt;
-  {
-    const int NG = B * Hkv;
-    int bid = blockIdx.x;
-    int gid, within;
-    if ((NG & 7) == 0) {
-      gid = (bid >> 3) / nkt * 8 + (bid & 7);
-      within = (bid >> 3) % nkt;
-    } else {
-      gid = bid / nkt;
-      within = bid % nkt;
-    }
-    b = gid / Hkv;
-    hkv = gid % Hkv;
-    kt = within;
-  }
+  const GroupBlock gb = xcd_remap(blockIdx.x, B * Hkv, nkt);
+  const int b = gb.gid / Hkv;
+  const int hkv = gb.gid % Hkv;
+  const int kt = gb.within;
 
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
@@ -183,43 +167,13 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
   const int nqt = (qcap - qstart + 63) / 64;
   const int niter = group * nqt;
 
-  // staging via LDS-DMA (st_idx subtile image;
-  // conflict-free), one (h, q-tile) AHEAD so global latency hides behind
-  // a full tile of MFMA
-  // LDS-DMA staging (global_load_lds; see attention_fwd.hip): the next
-  // (h, q-tile)'s Q/dO tiles stream into the other buffer with no staging
-  // registers and no vmcnt park; the per-lane global slot is pre-XOR'd so
-  // the contiguous landing equals the st_idx subtile image.
-  constexpr int nslot = D >> 3;
-  constexpr int ncw = nslot >> 2;
-  const int srow_half = lane >> 1;       // subtile-half row within chunk
-  const int scol_half = (lane & 1) * 8;  // 8-col half within subtile
+  // the next (h, q-tile)'s Q/dO tiles stream into the other buffer one
+  // iteration AHEAD, so global latency hides behind a full tile of MFMA
   auto stage_qdo = [&](int it, int buf) {
-    const int hh = hkv * group + it / nqt;
-    const int qt = qstart + (it % nqt) * 64;
-    const short* qbse = q + ((int64_t)b * S * Hq + hh) * D;
-    const short* dbse = dout + ((int64_t)b * S * Hq + hh) * D;
-#pragma unroll
-    for (int i = 0; i < ncw; ++i) {
-      const int ch = wid * ncw + i;
-      const int row = (ch & 1) * 32 + srow_half;
-      int r = qt + row;
-      if (r >= S) r = S - 1;
-      const int64_t goff =
-          (int64_t)r * strideS_q + (ch >> 1) * 16 + scol_half;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(qbse +
-                                                                  goff),
-          (__attribute__((address_space(3))) unsigned int*)(q_lds[buf] +
-                                                            ch * 512),
-          16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(dbse +
-                                                                  goff),
-          (__attribute__((address_space(3))) unsigned int*)(do_lds[buf] +
-                                                            ch * 512),
-          16, 0, 0);
-    }
+    const int64_t hoff = ((int64_t)b * S * Hq + hkv * group + it / nqt) * D;
+    stage_tile_pair<D>(q + hoff, dout + hoff, strideS_q,
+                       qstart + (it % nqt) * 64, S, q_lds[buf], do_lds[buf],
+                       wid, lane);
   };
   // lse lands pre-multiplied by log2(e), delta by scale
   auto stage_lse = [&](int it, int buf) {
@@ -279,10 +233,10 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
             dol + st_idx(qra, c * 32 + lg * 8));
         bf16x8 do1 = *reinterpret_cast<const bf16x8*>(
             dol + st_idx(qrb, c * 32 + lg * 8));
-        sa0 = mfma16b(qa0, kf[c], sa0);
-        sa1 = mfma16b(qa1, kf[c], sa1);
-        da0 = mfma16b(do0, vf[c], da0);
-        da1 = mfma16b(do1, vf[c], da1);
+        sa0 = mfma16(qa0, kf[c], sa0);
+        sa1 = mfma16(qa1, kf[c], sa1);
+        da0 = mfma16(do0, vf[c], da0);
+        da1 = mfma16(do1, vf[c], da1);
       }
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
@@ -328,10 +282,10 @@ __global__ void __launch_bounds__(256, 2) attn_dkdv_kernel(
       for (int kc = 0; kc < 2; ++kc) {
         bf16x8 dofr = tr16_frag_st(dol, kc * 32 + lg * 8, dt * 16, l15);
         bf16x8 qfr = tr16_frag_st(ql, kc * 32 + lg * 8, dt * 16, l15);
-        dvacc[dt] = mfma16b(__builtin_bit_cast(bf16x8, pk_p[kc]), dofr,
-                            dvacc[dt]);
-        dkacc[dt] = mfma16b(__builtin_bit_cast(bf16x8, pk_ds[kc]), qfr,
-                            dkacc[dt]);
+        dvacc[dt] = mfma16(__builtin_bit_cast(bf16x8, pk_p[kc]), dofr,
+                           dvacc[dt]);
+        dkacc[dt] = mfma16(__builtin_bit_cast(bf16x8, pk_ds[kc]), qfr,
+                           dkacc[dt]);
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -366,31 +320,18 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
   // double-buffered K and V tiles (st_idx subtile image): K serves
   // the S^T A-fragments (b128 row reads) AND the dQ B-fragments (tr16
   // transpose reads); V serves the dP^T A-fragments
-  __shared__ short k_lds[2][64 * D];
-  __shared__ short v_lds[2][64 * D];
+  __shared__ short k_lds[2][KVBLK * D];
+  __shared__ short v_lds[2][KVBLK * D];
 
-  const int ntq = (S + 127) / 128;
+  const int ntq = (S + QBLK - 1) / QBLK;
   const int gqa = Hq / Hkv;
   const int bpg = gqa * ntq;
 
-  int b, h, qtile;
-  {
-    const int NG = B * Hkv;
-    int bid = blockIdx.x;
-    int gid, within;
-    if ((NG & 7) == 0) {
-      gid = (bid >> 3) / bpg * 8 + (bid & 7);
-      within = (bid >> 3) % bpg;
-    } else {
-      gid = bid / bpg;
-      within = bid % bpg;
-    }
-    b = gid / Hkv;
-    const int hkv0 = gid % Hkv;
-    h = hkv0 * gqa + within / ntq;
-    qtile = within % ntq;
-  }
-  const int hkv = h / gqa;
+  const GroupBlock gb = xcd_remap(blockIdx.x, B * Hkv, bpg);
+  const int b = gb.gid / Hkv;
+  const int hkv = gb.gid % Hkv;
+  const int h = hkv * gqa + gb.within / ntq;
+  const int qtile = gb.within % ntq;
 
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
@@ -398,10 +339,9 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
   const int l15 = lane & 15;
   const int lg = lane >> 4;
 
-  // this wave's 32 q rows as two 16-row groups interleaved across the
-  // block (rows w*16 and w*16+64) — causal activity is then uniform
-  // across waves (no per-tile barrier idling); see attention_fwd.hip
-  const int rowb[2] = {qtile * 128 + wid * 16, qtile * 128 + 64 + wid * 16};
+  // this wave's 32 q rows: two interleaved 16-row groups (qgroup_row)
+  const int q0 = qtile * QBLK;
+  const int rowb[2] = {qgroup_row(q0, wid, 0), qgroup_row(q0, wid, 1)};
   constexpr int nd16 = D >> 4, nkc = D >> 5;
   const float c2 = scale * LOG2E;
   const int64_t strideS_q = (int64_t)Hq * D;
@@ -439,60 +379,23 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
 #pragma unroll
     for (int nq = 0; nq < 2; ++nq) dqacc[dt][nq] = {0.f, 0.f, 0.f, 0.f};
 
-  const int kv_end = min(S, qtile * 128 + 128);
-  const int ntiles = (kv_end + 63) / 64;
+  const int kv_end = min(S, q0 + QBLK);
+  const int ntiles = (kv_end + KVBLK - 1) / KVBLK;
+  int dstart[2], dsmax[2];
+  const int t0 =
+      doc_window<DOC>(doc_start, b, S, q0, wid, l15, dstart, dsmax);
 
-  // DOC: per-lane first visible key of each q row, the row group's largest
-  // one (its last valid row) for the wave-uniform diag test, and the
-  // block's first K/V tile — as in attention_fwd.hip
-  int dstart[2] = {0, 0}, dsmax[2] = {0, 0};
-  int t0 = 0;
-  if (DOC) {
-    const int* dsb = doc_start + (int64_t)b * S;
-#pragma unroll
-    for (int nq = 0; nq < 2; ++nq) {
-      dstart[nq] = dsb[min(rowb[nq] + l15, S - 1)];
-      dsmax[nq] = dsb[min(rowb[nq] + 15, S - 1)];
-    }
-    t0 = min(max(dsb[qtile * 128], 0), qtile * 128) / 64;  // in bounds
-  }
-
-  // LDS-DMA staging (global_load_lds; see attention_fwd.hip)
-  constexpr int nslot = D >> 3;
-  constexpr int ncw = nslot >> 2;
-  const int srow_half = lane >> 1;       // subtile-half row within chunk
-  const int scol_half = (lane & 1) * 8;  // 8-col half within subtile
-  auto stage_k = [&](int kv0s, int buf) {
-#pragma unroll
-    for (int i = 0; i < ncw; ++i) {
-      const int ch = wid * ncw + i;
-      const int key = (ch & 1) * 32 + srow_half;
-      int kg = kv0s + key;
-      if (kg >= S) kg = S - 1;
-      const int64_t goff =
-          (int64_t)kg * strideS_kv + (ch >> 1) * 16 + scol_half;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(kb + goff),
-          (__attribute__((address_space(3))) unsigned int*)(k_lds[buf] +
-                                                            ch * 512),
-          16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(vb + goff),
-          (__attribute__((address_space(3))) unsigned int*)(v_lds[buf] +
-                                                            ch * 512),
-          16, 0, 0);
-    }
+  auto stage_kv = [&](int t, int buf) {
+    stage_tile_pair<D>(kb, vb, strideS_kv, t * KVBLK, S, k_lds[buf],
+                       v_lds[buf], wid, lane);
   };
-
-  // the first tile visited lands in buffer 0 whatever its parity: the
-  // buffer index counts from t0, not from tile 0
-  stage_k(t0 * 64, 0);
+  stage_kv(t0, 0);
   __syncthreads();
 
   for (int t = t0; t < ntiles; ++t) {
-    const int kv0 = t * 64;
-    const int buf = (t - t0) & 1;
-    if (t + 1 < ntiles) stage_k((t + 1) * 64, buf ^ 1);
+    const int kv0 = t * KVBLK;
+    const int buf = tile_buf(t, t0);
+    if (t + 1 < ntiles) stage_kv(t + 1, buf ^ 1);
 
     // group 0 (lower rows) drops out at the final diagonal tiles; group 1
     // is live for every tile — uniform across waves (no barrier idling)
@@ -505,7 +408,7 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
       // ---- per mt: S^T = mfma(K_perm, Q), dP^T = mfma(V_perm, dO), then
       // immediately exp/pack dS into the dQ MFMA's A operand (keys in
       // kc*32+lg*8+j order via perm16) — keeps only one mt of S/dP live ----
-      const bool smask = (kv_end < kv0 + 64);
+      const bool smask = (kv_end < kv0 + KVBLK);
       u32x4 pk_ds[2][2];  // [nq][kc]
       const short* kl = k_lds[buf];
       const short* vl = v_lds[buf];
@@ -521,17 +424,17 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
               kl + st_idx(kr, c * 32 + lg * 8));
           bf16x8 va = *reinterpret_cast<const bf16x8*>(
               vl + st_idx(kr, c * 32 + lg * 8));
-          s0 = mfma16b(ka, qf[0][c], s0);
-          d0 = mfma16b(va, dof[0][c], d0);
-          s1 = mfma16b(ka, qf[1][c], s1);
-          d1 = mfma16b(va, dof[1][c], d1);
+          s0 = mfma16(ka, qf[0][c], s0);
+          d0 = mfma16(va, dof[0][c], d0);
+          s1 = mfma16(ka, qf[1][c], s1);
+          d1 = mfma16(va, dof[1][c], d1);
         }
         const int koff = cpos16(mt, lg);
         const int kc = mt >> 1, rp = (mt & 1) * 2;
 #pragma unroll
         for (int nq = 0; nq < 2; ++nq) {
           const int qrow = rowb[nq] + l15;
-          const bool diag = (kv0 + 63 > rowb[nq]) || smask ||
+          const bool diag = (kv0 + KVBLK - 1 > rowb[nq]) || smask ||
                             (DOC && dsmax[nq] > kv0);
           const f32x4 sv = nq ? s1 : s0;
           const f32x4 dv = nq ? d1 : d0;
@@ -565,18 +468,11 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
       for (int dt = 0; dt < nd16; ++dt) {
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
-#ifdef DQ_SCALAR_B
-          bf16x8 kfr;
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            kfr[j] = kl[st_idx(kc * 32 + lg * 8 + j, dt * 16 + l15)];
-#else
           bf16x8 kfr = tr16_frag_st(kl, kc * 32 + lg * 8, dt * 16, l15);
-#endif
-          dqacc[dt][0] = mfma16b(__builtin_bit_cast(bf16x8, pk_ds[0][kc]),
-                                 kfr, dqacc[dt][0]);
-          dqacc[dt][1] = mfma16b(__builtin_bit_cast(bf16x8, pk_ds[1][kc]),
-                                 kfr, dqacc[dt][1]);
+          dqacc[dt][0] = mfma16(__builtin_bit_cast(bf16x8, pk_ds[0][kc]),
+                                kfr, dqacc[dt][0]);
+          dqacc[dt][1] = mfma16(__builtin_bit_cast(bf16x8, pk_ds[1][kc]),
+                                kfr, dqacc[dt][1]);
         }
       }
       __builtin_amdgcn_s_setprio(0);
@@ -601,52 +497,41 @@ __global__ void __launch_bounds__(256, 2) attn_dq_kernel(
 }
 
 namespace {
-template <bool DOC>
-void bwd_launch(const void* dout, const void* q, const void* k, const void* v,
-                const void* o, const float* lse, float* delta, void* dq,
-                void* dk, void* dv, const int* doc_start, const int* doc_end,
-                int B, int S, int Hq, int Hkv, int D, float scale,
-                hipStream_t stream) {
+template <int D, bool DOC>
+void bwd_launch(const short* dout, const short* q, const short* k,
+                const short* v, const short* o, const float* lse,
+                float* delta, short* dq, short* dk, short* dv,
+                const int* doc_start, const int* doc_end, int B, int S,
+                int Hq, int Hkv, float scale, hipStream_t stream) {
   int64_t nrows = (int64_t)B * S * Hq;
   int64_t dwant = (nrows + 15) / 16;
   int dgrid = (int)(dwant < 2048 ? (dwant < 1 ? 1 : dwant) : 2048);
-  // bindings.cpp admits D of 64 or 128 only
-  const bool d64 = D == 64;
-  hipLaunchKernelGGL(d64 ? attn_delta_kernel<64> : attn_delta_kernel<128>,
-                     dim3(dgrid), dim3(256), 0, stream, (const short*)dout,
-                     (const short*)o, delta, B, S, Hq);
+  hipLaunchKernelGGL(attn_delta_kernel<D>, dim3(dgrid), dim3(256), 0, stream,
+                     dout, o, delta, B, S, Hq);
   int nkt = (S + 63) / 64;
-  auto dkdv = d64 ? attn_dkdv_kernel<64, DOC> : attn_dkdv_kernel<128, DOC>;
-  hipLaunchKernelGGL(dkdv, dim3((uint32_t)((int64_t)B * Hkv * nkt)),
-                     dim3(256), 0, stream, (const short*)dout,
-                     (const short*)q, (const short*)k, (const short*)v, lse,
-                     delta, (short*)dk, (short*)dv, B, S, Hq, Hkv, scale,
-                     doc_end);
-  int ntq = (S + 127) / 128;
-  auto dqk = d64 ? attn_dq_kernel<64, DOC> : attn_dq_kernel<128, DOC>;
-  hipLaunchKernelGGL(dqk, dim3((uint32_t)((int64_t)B * Hq * ntq)), dim3(256), 0,
-                     stream, (const short*)dout, (const short*)q,
-                     (const short*)k, (const short*)v, lse, delta, (short*)dq,
-                     B, S, Hq, Hkv, scale, doc_start);
+  hipLaunchKernelGGL((attn_dkdv_kernel<D, DOC>),
+                     dim3((uint32_t)((int64_t)B * Hkv * nkt)), dim3(256), 0,
+                     stream, dout, q, k, v, lse, delta, dk, dv, B, S, Hq, Hkv,
+                     scale, doc_end);
+  int ntq = (S + QBLK - 1) / QBLK;
+  hipLaunchKernelGGL((attn_dq_kernel<D, DOC>),
+                     dim3((uint32_t)((int64_t)B * Hq * ntq)), dim3(256), 0,
+                     stream, dout, q, k, v, lse, delta, dq, B, S, Hq, Hkv,
+                     scale, doc_start);
 }
 }  // namespace
 
-extern "C" {
-void attn_bwd_launch(const void* dout, const void* q, const void* k,
-                     const void* v, const void* o, const float* lse,
-                     float* delta, void* dq, void* dk, void* dv, int B, int S,
-                     int Hq, int Hkv, int D, float scale, hipStream_t stream) {
-  bwd_launch<false>(dout, q, k, v, o, lse, delta, dq, dk, dv, nullptr, nullptr,
-                    B, S, Hq, Hkv, D, scale, stream);
-}
-
-void attn_bwd_doc_launch(const void* dout, const void* q, const void* k,
-                         const void* v, const void* o, const float* lse,
-                         float* delta, void* dq, void* dk, void* dv,
-                         const int* doc_start, const int* doc_end, int B,
-                         int S, int Hq, int Hkv, int D, float scale,
-                         hipStream_t stream) {
-  bwd_launch<true>(dout, q, k, v, o, lse, delta, dq, dk, dv, doc_start,
-                   doc_end, B, S, Hq, Hkv, D, scale, stream);
-}
+extern "C" void attn_bwd_launch(const void* dout, const void* q, const void* k,
+                                const void* v, const void* o, const float* lse,
+                                float* delta, void* dq, void* dk, void* dv,
+                                const int* doc_start, const int* doc_end,
+                                int B, int S, int Hq, int Hkv, int D,
+                                float scale, hipStream_t stream) {
+  // bindings.cpp admits D of 64 or 128 only, and both tables or neither
+  const bool doc = doc_start != nullptr;
+  auto fn = doc ? (D == 64 ? bwd_launch<64, true> : bwd_launch<128, true>)
+                : (D == 64 ? bwd_launch<64, false> : bwd_launch<128, false>);
+  fn((const short*)dout, (const short*)q, (const short*)k, (const short*)v,
+     (const short*)o, lse, delta, (short*)dq, (short*)dk, (short*)dv,
+     doc_start, doc_end, B, S, Hq, Hkv, scale, stream);
 }

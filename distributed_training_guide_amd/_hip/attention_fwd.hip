@@ -1,6 +1,6 @@
-// Causal flash-attention forward for gfx950 — v5: swapped-operand S^T MFMA
-// with in-register P, double-buffered LDS K/V tiles prefetched a full tile
-// ahead (T14), one barrier per tile.
+// Causal flash-attention forward for gfx950: swapped-operand S^T MFMA with
+// in-register P, double-buffered LDS K/V tiles DMA-staged a full tile ahead,
+// one barrier per tile.
 //
 // Replaces the reference's flash-attn-2 dependency
 // (attn_implementation="flash_attention_2", 05:93 / 06:73 / 07:71 —
@@ -11,48 +11,38 @@
 // each query to its own document of a packed row (flash-attn-2's varlen
 // masking). Saves lse [B,Hq,S] f32 for the backward.
 //
-// v3 design (guide §5.5 / §5 "common mistakes"):
+// Design (guide §5.5 / §5 "common mistakes"):
 //   * S^T = mfma(A=K, B=Q): the C fragment then holds qrow = lane&15 —
 //     softmax rows are (mostly) lane-local: 16 values in registers + two
 //     shfl_xor steps, instead of 16-lane tree reductions per row.
-//   * Key-permuted A fragments: K rows are fed to the QK^T MFMA in an
-//     order chosen so the C-fragment's per-lane key positions equal the
-//     B-operand layout that P^T needs for the P·V MFMA. P therefore never
-//     leaves registers: exp -> v_cvt_pk_bf16_f32 -> B fragment. No P LDS
-//     round-trip, no block barrier between QK^T and P·V.
-//   * K and V are staged into double-buffered LDS, with the global loads
-//     for tile t+1 issued at the TOP of tile t's compute: the ~200-900cy
-//     global latency lands behind a full tile of MFMA (T14), and the
-//     A-fragment reads become ~50cy ds_read_b128 the compiler interleaves
-//     with the MFMA stream (PMC before this change: 67% SQ_WAIT_ANY on the
-//     direct-global K path). K image row-major 16B-slot-swizzled
-//     (conflict-free writes AND reads); the XCD-aware remap keeps a
-//     (b,kv-head) group's K/V on one XCD's L2.
-//   * V is staged TRANSPOSED into double-buffered LDS (v^T[d][key], key
-//     index XOR-swizzled): the P·V MFMA's A operand needs 8 consecutive
-//     keys per lane, which only a transposed image can serve as
-//     ds_read_b128. One barrier per KV tile (ping-pong buffers).
-//   * O^T accumulates in C fragments (qrow = lane&15 throughout), scale
-//     folded into exp2f, epilogue writes 4 consecutive d per lane (b64).
+//   * Key-permuted A fragments (perm16): K rows are fed to the QK^T MFMA in
+//     an order chosen so the C-fragment's per-lane key positions (cpos16)
+//     equal the B-operand layout that P^T needs for the P·V MFMA. P
+//     therefore never leaves registers: exp -> v_cvt_pk_bf16_f32 -> B
+//     fragment. No P LDS round-trip, no block barrier between QK^T and P·V.
+//   * K and V tiles are both ROW-major st_idx images (16-col subtiles) in
+//     double-buffered LDS, landed by LDS-DMA (stage_tile_pair) with tile
+//     t+1 issued at the TOP of tile t's compute: the ~200-900cy global
+//     latency lands behind a full tile of MFMA (T14; PMC before: 67%
+//     SQ_WAIT_ANY on the direct-global K path). One barrier per KV tile
+//     (ping-pong buffers).
+//   * K A-fragments are b128 row reads of that image (~50cy, interleaved
+//     with the MFMA stream by the compiler); V^T A-fragments — 8
+//     consecutive keys per lane — come from the same kind of image through
+//     the tr16 hardware-transpose read (tr16_frag_st): no transposed copy.
+//   * The XCD-aware remap (xcd_remap) keeps a (b,kv-head) group's K/V on
+//     one XCD's L2.
+//   * O^T accumulates in C fragments (qrow = lane&15 throughout); the
+//     softmax is one fma (scale*log2(e) as its multiplier) and one raw
+//     v_exp_f32 (__builtin_amdgcn_exp2f) per score; the epilogue writes 4
+//     consecutive d per lane (b64).
 //
 // MFMA fragment maps (gfx950 v_mfma_f32_16x16x32_bf16):
 //   A[m][k]: lane l holds m = l&15, k = (l>>4)*8 + j (j=0..7)
 //   B[k][n]: lane l holds n = l&15, k = (l>>4)*8 + j
 //   C/D     : lane l holds n = l&15, m = (l>>4)*4 + r (r=0..3)
-#include "common.h"
+#include "attention_common.h"
 #include "launchers.h"
-
-using bf16x8 = s16x8;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4v;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-#define QBLK 128   // q rows per block (32 per wave)
-#define KVBLK 64   // keys per LDS tile
-#define LOG2E 1.4426950408889634f
 
 // DOC adds the intra-document mask of packed rows: doc_start [B,S] int32
 // holds, per token, the index of the first token of its document; query i
@@ -79,27 +69,11 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   const int gqa = Hq / Hkv;
   const int bpg = gqa * ntq;  // blocks per (b, hkv) group
 
-  // XCD-aware remap (guide T1): all blocks of one (b,hkv) group land on one
-  // XCD so its K/V stay in that XCD's L2. Dispatcher places block i on XCD
-  // i%8 (performance only, never correctness).
-  int b, h, qtile;
-  {
-    const int NG = B * Hkv;
-    int bid = blockIdx.x;
-    int gid, within;
-    if ((NG & 7) == 0) {
-      gid = (bid >> 3) / bpg * 8 + (bid & 7);
-      within = (bid >> 3) % bpg;
-    } else {
-      gid = bid / bpg;
-      within = bid % bpg;
-    }
-    b = gid / Hkv;
-    const int hkv = gid % Hkv;
-    h = hkv * gqa + within / ntq;
-    qtile = within % ntq;
-  }
-  const int hkv = h / gqa;
+  const GroupBlock gb = xcd_remap(blockIdx.x, B * Hkv, bpg);
+  const int b = gb.gid / Hkv;
+  const int hkv = gb.gid % Hkv;
+  const int h = hkv * gqa + gb.within / ntq;
+  const int qtile = gb.within % ntq;
 
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
@@ -107,11 +81,9 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   const int l15 = lane & 15;
   const int lg = lane >> 4;
 
-  // this wave's 32 q rows, as two 16-row groups INTERLEAVED across the
-  // block (rows w*16 and w*16+64): every wave then touches both halves of
-  // the q range, so causal tile-skipping is uniform across waves and no
-  // wave idles at the per-tile barrier (guide: wave load balance)
-  const int rowb[2] = {qtile * QBLK + wid * 16, qtile * QBLK + 64 + wid * 16};
+  // this wave's 32 q rows: two interleaved 16-row groups (qgroup_row)
+  const int q0 = qtile * QBLK;
+  const int rowb[2] = {qgroup_row(q0, wid, 0), qgroup_row(q0, wid, 1)};
   constexpr int nd16 = D >> 4;             // 16-d tiles (8 for D=128)
   constexpr int nkc = D >> 5;              // 32-d MFMA K chunks
   const int64_t strideS_q = (int64_t)Hq * D;
@@ -132,20 +104,17 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
       qf[nq][kc] = *reinterpret_cast<const bf16x8*>(qp + kc * 32);
   }
 
-  // key permutation: C-fragment m-position p (= mt*16 + lg*4 + r) must hold
-  // key (mt>>1)*32 + lg*8 + (mt&1)*4 + r, so the packed P rows are already
-  // the B-operand key order (kc*32 + lg*8 + j). A-operand lane position is
-  // l15 = lg_c*4 + r of the C tile.
-  int kperm[4];  // key offset of A-fragment row l15 in tile mt
+  // A-fragment row l15 of tile mt carries key perm16(mt, l15), so the packed
+  // P rows are already in the P·V MFMA's B-operand key order; cpos16 is the
+  // matching first key of this lane's C positions (for the masks).
+  // Computed once here: with the calls inside the tile loop the compiler
+  // spends 4-12 more VGPRs on this kernel.
+  int kperm[4], ckey[4];
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-    kperm[mt] = (mt >> 1) * 32 + (l15 >> 2) * 8 + (mt & 1) * 4 + (l15 & 3);
-  // per-lane key offsets of the C fragment (for causal masking):
-  // key(mt, r) = (mt>>1)*32 + lg*8 + (mt&1)*4 + r
-  int ckey[4];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-    ckey[mt] = (mt >> 1) * 32 + lg * 8 + (mt & 1) * 4;
+  for (int mt = 0; mt < 4; ++mt) {
+    kperm[mt] = perm16(mt, l15);
+    ckey[mt] = cpos16(mt, lg);
+  }
 
   // O^T accumulators: [d tile][nq] C frags; lane: qrow=l15, d=lg*4+r
   f32x4 oacc[nd16][2];
@@ -159,72 +128,26 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   float mcrow[2] = {-INFINITY, -INFINITY};
   float lrow[2] = {0.f, 0.f};
 
-  const int kv_end = min(S, qtile * QBLK + QBLK);
+  const int kv_end = min(S, q0 + QBLK);
   const int ntiles = (kv_end + KVBLK - 1) / KVBLK;
   const float c = scale * LOG2E;
-  (void)hkv;
+  int dstart[2], dsmax[2];
+  const int t0 =
+      doc_window<DOC>(doc_start, b, S, q0, wid, l15, dstart, dsmax);
 
-  // DOC: per-lane first visible key of each q row (clamped like qrow), the
-  // row group's largest one (its last valid row — doc_start is monotone)
-  // for the wave-uniform need_mask test, and the block's first K/V tile:
-  // no row of the q tile sees a key before its first row's document.
-  int dstart[2] = {0, 0}, dsmax[2] = {0, 0};
-  int t0 = 0;
-  if (DOC) {
-    const int* dsb = doc_start + (int64_t)b * S;
-#pragma unroll
-    for (int nq = 0; nq < 2; ++nq) {
-      dstart[nq] = dsb[min(rowb[nq] + l15, S - 1)];
-      dsmax[nq] = dsb[min(rowb[nq] + 15, S - 1)];
-    }
-    // clamped to the contract (0 <= doc_start[i] <= i) so that a bad table
-    // cannot move the staging loads out of bounds
-    t0 = min(max(dsb[qtile * QBLK], 0), qtile * QBLK) / KVBLK;
-  }
-
-  // ---- staging via LDS-DMA (global_load_lds, probed: data lands at
-  // lds_base + lane*16 with per-lane global sources — tools/gldsprobe.hip):
-  // no staging registers, no ds_write pass, no vmcnt park.  The per-lane
-  // global slot is pre-XOR'd so the contiguous landing equals the
-  // st_idx subtile image; tile t+1's DMA issues at the top of tile t and
-  // completes under a full tile of MFMA before the end-of-tile barrier.
-  constexpr int nslot = D >> 3;
-  constexpr int ncw = nslot >> 2;  // chunks per wave per tensor
-  const int srow_half = lane >> 1;       // subtile-half row within chunk
-  const int scol_half = (lane & 1) * 8;  // 8-col half within subtile
-  auto stage_kv = [&](int kv0, int buf) {
-#pragma unroll
-    for (int i = 0; i < ncw; ++i) {
-      const int ch = wid * ncw + i;
-      const int key = (ch & 1) * 32 + srow_half;
-      int kg = kv0 + key;
-      if (kg >= S) kg = S - 1;
-      const int64_t goff =
-          (int64_t)kg * strideS_kv + (ch >> 1) * 16 + scol_half;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(kb + goff),
-          (__attribute__((address_space(3))) unsigned int*)(k_lds[buf] +
-                                                            ch * 512),
-          16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(vb + goff),
-          (__attribute__((address_space(3))) unsigned int*)(v_lds[buf] +
-                                                            ch * 512),
-          16, 0, 0);
-    }
+  // tile t+1's DMA issues at the top of tile t and completes under a full
+  // tile of MFMA before the end-of-tile barrier
+  auto stage_kv = [&](int t, int buf) {
+    stage_tile_pair<D>(kb, vb, strideS_kv, t * KVBLK, S, k_lds[buf],
+                       v_lds[buf], wid, lane);
   };
-
-  // the first tile visited lands in buffer 0 whatever its parity: the
-  // buffer index counts from t0, not from tile 0
-  stage_kv(t0 * KVBLK, 0);
+  stage_kv(t0, 0);
   __syncthreads();
 
   for (int t = t0; t < ntiles; ++t) {
     const int kv0 = t * KVBLK;
-    const int buf = (t - t0) & 1;
-    // stage next tile into the other buffer (global loads issue before the
-    // MFMA stream — T14 spirit; ds_writes don't touch the compute buffer)
-    if (t + 1 < ntiles) stage_kv((t + 1) * KVBLK, buf ^ 1);
+    const int buf = tile_buf(t, t0);
+    if (t + 1 < ntiles) stage_kv(t + 1, buf ^ 1);
 
     // Both 16-row groups are computed unconditionally on every tile: an
     // `if (act0)`-guarded MFMA accumulation (skipping group 0 on its
@@ -357,10 +280,10 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
     short* op = o + ((int64_t)b * S * Hq + (int64_t)qrow * Hq + h) * D;
 #pragma unroll
     for (int dt = 0; dt < nd16; ++dt) {
-      s16x4v outv;
+      s16x4 outv;
 #pragma unroll
       for (int r = 0; r < 4; ++r) outv[r] = f2bf(oacc[dt][nq][r] * invl);
-      *reinterpret_cast<s16x4v*>(op + dt * 16 + lg * 4) = outv;
+      *reinterpret_cast<s16x4*>(op + dt * 16 + lg * 4) = outv;
     }
     if (lg == 0)
       lse_out[((int64_t)b * Hq + h) * S + qrow] =
@@ -368,34 +291,19 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(
   }
 }
 
-namespace {
-template <bool DOC>
-void fwd_launch(const void* q, const void* k, const void* v, void* o,
-                float* lse, const int* doc_start, int B, int S, int Hq,
-                int Hkv, int D, float scale, hipStream_t stream) {
+extern "C" void attn_fwd_launch(const void* q, const void* k, const void* v,
+                                void* o, float* lse, const int* doc_start,
+                                int B, int S, int Hq, int Hkv, int D,
+                                float scale, hipStream_t stream) {
   int ntiles = (S + QBLK - 1) / QBLK;
   int64_t grid = (int64_t)B * Hq * ntiles;
   // bindings.cpp admits D of 64 or 128 only
-  auto kern = D == 64 ? attn_fwd_kernel<64, DOC> : attn_fwd_kernel<128, DOC>;
+  auto kern = doc_start
+                  ? (D == 64 ? attn_fwd_kernel<64, true>
+                             : attn_fwd_kernel<128, true>)
+                  : (D == 64 ? attn_fwd_kernel<64, false>
+                             : attn_fwd_kernel<128, false>);
   hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, stream,
                      (const short*)q, (const short*)k, (const short*)v,
                      (short*)o, lse, B, S, Hq, Hkv, scale, doc_start);
-}
-}  // namespace
-
-extern "C" {
-void attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
-                     float* lse, int B, int S, int Hq, int Hkv, int D,
-                     float scale, hipStream_t stream) {
-  fwd_launch<false>(q, k, v, o, lse, nullptr, B, S, Hq, Hkv, D, scale,
-                    stream);
-}
-
-void attn_fwd_doc_launch(const void* q, const void* k, const void* v, void* o,
-                         float* lse, const int* doc_start, int B, int S,
-                         int Hq, int Hkv, int D, float scale,
-                         hipStream_t stream) {
-  fwd_launch<true>(q, k, v, o, lse, doc_start, B, S, Hq, Hkv, D, scale,
-                   stream);
-}
 }

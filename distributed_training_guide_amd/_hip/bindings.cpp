@@ -405,50 +405,9 @@ void grad_scale_(torch::Tensor descs, int64_t nchunks, torch::Tensor sq_total,
 }
 
 // ---------------- attention ----------------
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, double scale) {
-  CHECK_BF16_CONTIG(q);
-  CHECK_BF16_CONTIG(k);
-  CHECK_BF16_CONTIG(v);
-  TORCH_CHECK(q.dim() == 4, "q must be [B,S,Hq,D]");
-  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(2);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
-  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({(int64_t)B, (int64_t)Hq, (int64_t)S},
-                          q.options().dtype(torch::kFloat));
-  attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                  lse.data_ptr<float>(), B, S, Hq, Hkv, D, (float)scale,
-                  cur_stream());
-  return {o, lse};
-}
-
-std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
-                                    torch::Tensor k, torch::Tensor v,
-                                    torch::Tensor o, torch::Tensor lse,
-                                    double scale) {
-  CHECK_BF16_CONTIG(dout);
-  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(2);
-  auto dq = torch::empty_like(q);
-  auto dk = torch::empty_like(k);
-  auto dv = torch::empty_like(v);
-  auto delta = torch::empty({(int64_t)B, (int64_t)Hq, (int64_t)S},
-                            q.options().dtype(torch::kFloat));
-  attn_bwd_launch(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                  o.data_ptr(), lse.data_ptr<float>(),
-                  delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
-                  dv.data_ptr(), B, S, Hq, Hkv, D, (float)scale,
-                  cur_stream());
-  return {dq, dk, dv};
-}
-
-// document-masked variants: doc_start / doc_end are the [B,S] int32 tables
-// of ops/doc_mask.py (their contents are the caller's contract; the
-// kernels only keep a bad table from moving loads out of bounds)
+// doc_start / doc_end are the [B,S] int32 tables of ops/doc_mask.py (their
+// contents are the caller's contract; the kernels only keep a bad table
+// from moving loads out of bounds); an undefined tensor = plain causal
 #define CHECK_DOC_TABLE(t, q)                                              \
   TORCH_CHECK((t).is_cuda() && (t).device() == (q).device(),               \
               #t " must be on q's device");                                \
@@ -457,53 +416,111 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
   TORCH_CHECK((t).dim() == 2 && (t).size(0) == (q).size(0) &&              \
               (t).size(1) == (q).size(1), #t " must be [B,S]")
 
-std::vector<torch::Tensor> attn_fwd_doc(torch::Tensor q, torch::Tensor k,
-                                        torch::Tensor v,
-                                        torch::Tensor doc_start,
-                                        double scale) {
+struct AttnDims {
+  int B, S, Hq, Hkv, D;
+};
+
+// the checks every attention entry point makes of q / k / v
+AttnDims attn_check_qkv(const torch::Tensor& q, const torch::Tensor& k,
+                        const torch::Tensor& v) {
   CHECK_BF16_CONTIG(q);
   CHECK_BF16_CONTIG(k);
   CHECK_BF16_CONTIG(v);
   TORCH_CHECK(q.dim() == 4, "q must be [B,S,Hq,D]");
-  CHECK_DOC_TABLE(doc_start, q);
-  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(2);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
-  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+  TORCH_CHECK(k.dim() == 4 && k.size(0) == q.size(0) &&
+                  k.size(1) == q.size(1) && k.size(3) == q.size(3),
+              "k must be [B,S,Hkv,D]");
+  TORCH_CHECK(v.sizes() == k.sizes(), "v must be [B,S,Hkv,D]");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(),
+              "k and v must be on q's device");
+  const AttnDims d = {(int)q.size(0), (int)q.size(1), (int)q.size(2),
+                      (int)k.size(2), (int)q.size(3)};
+  TORCH_CHECK(d.Hq % d.Hkv == 0, "GQA requires Hq % Hkv == 0");
+  TORCH_CHECK(d.D == 64 || d.D == 128, "head dim must be 64 or 128");
+  return d;
+}
+
+std::vector<torch::Tensor> attn_fwd_impl(const torch::Tensor& q,
+                                         const torch::Tensor& k,
+                                         const torch::Tensor& v,
+                                         const torch::Tensor& doc_start,
+                                         double scale) {
+  const AttnDims d = attn_check_qkv(q, k, v);
+  const bool doc = doc_start.defined();
+  if (doc) {
+    CHECK_DOC_TABLE(doc_start, q);
+  }
   auto o = torch::empty_like(q);
-  auto lse = torch::empty({(int64_t)B, (int64_t)Hq, (int64_t)S},
+  auto lse = torch::empty({(int64_t)d.B, (int64_t)d.Hq, (int64_t)d.S},
                           q.options().dtype(torch::kFloat));
-  attn_fwd_doc_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                      lse.data_ptr<float>(), doc_start.data_ptr<int>(), B, S,
-                      Hq, Hkv, D, (float)scale, cur_stream());
+  attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                  lse.data_ptr<float>(),
+                  doc ? doc_start.data_ptr<int>() : nullptr, d.B, d.S, d.Hq,
+                  d.Hkv, d.D, (float)scale, cur_stream());
   return {o, lse};
 }
 
+std::vector<torch::Tensor> attn_bwd_impl(
+    const torch::Tensor& dout, const torch::Tensor& q, const torch::Tensor& k,
+    const torch::Tensor& v, const torch::Tensor& o, const torch::Tensor& lse,
+    const torch::Tensor& doc_start, const torch::Tensor& doc_end,
+    double scale) {
+  const AttnDims d = attn_check_qkv(q, k, v);
+  CHECK_BF16_CONTIG(dout);
+  CHECK_BF16_CONTIG(o);
+  TORCH_CHECK(dout.sizes() == q.sizes() && o.sizes() == q.sizes(),
+              "dout and o must be [B,S,Hq,D] like q");
+  TORCH_CHECK(lse.is_cuda() && lse.dtype() == torch::kFloat &&
+                  lse.is_contiguous() && lse.dim() == 3 &&
+                  lse.size(0) == d.B && lse.size(1) == d.Hq &&
+                  lse.size(2) == d.S,
+              "lse must be a contiguous cuda f32 [B,Hq,S]");
+  TORCH_CHECK(dout.device() == q.device() && o.device() == q.device() &&
+                  lse.device() == q.device(),
+              "dout, o and lse must be on q's device");
+  const bool doc = doc_start.defined();
+  if (doc) {
+    CHECK_DOC_TABLE(doc_start, q);
+    CHECK_DOC_TABLE(doc_end, q);
+  }
+  auto dq = torch::empty_like(q);
+  auto dk = torch::empty_like(k);
+  auto dv = torch::empty_like(v);
+  auto delta = torch::empty({(int64_t)d.B, (int64_t)d.Hq, (int64_t)d.S},
+                            q.options().dtype(torch::kFloat));
+  attn_bwd_launch(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                  o.data_ptr(), lse.data_ptr<float>(),
+                  delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+                  dv.data_ptr(), doc ? doc_start.data_ptr<int>() : nullptr,
+                  doc ? doc_end.data_ptr<int>() : nullptr, d.B, d.S, d.Hq,
+                  d.Hkv, d.D, (float)scale, cur_stream());
+  return {dq, dk, dv};
+}
+
+// the Python-visible names: one pair per mode
+std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v, double scale) {
+  return attn_fwd_impl(q, k, v, torch::Tensor(), scale);
+}
+std::vector<torch::Tensor> attn_fwd_doc(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v,
+                                        torch::Tensor doc_start,
+                                        double scale) {
+  return attn_fwd_impl(q, k, v, doc_start, scale);
+}
+std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
+                                    torch::Tensor k, torch::Tensor v,
+                                    torch::Tensor o, torch::Tensor lse,
+                                    double scale) {
+  return attn_bwd_impl(dout, q, k, v, o, lse, torch::Tensor(), torch::Tensor(),
+                       scale);
+}
 std::vector<torch::Tensor> attn_bwd_doc(torch::Tensor dout, torch::Tensor q,
                                         torch::Tensor k, torch::Tensor v,
                                         torch::Tensor o, torch::Tensor lse,
                                         torch::Tensor doc_start,
                                         torch::Tensor doc_end, double scale) {
-  CHECK_BF16_CONTIG(dout);
-  TORCH_CHECK(q.dim() == 4, "q must be [B,S,Hq,D]");
-  CHECK_DOC_TABLE(doc_start, q);
-  CHECK_DOC_TABLE(doc_end, q);
-  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(2);
-  auto dq = torch::empty_like(q);
-  auto dk = torch::empty_like(k);
-  auto dv = torch::empty_like(v);
-  auto delta = torch::empty({(int64_t)B, (int64_t)Hq, (int64_t)S},
-                            q.options().dtype(torch::kFloat));
-  attn_bwd_doc_launch(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                      v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
-                      delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
-                      dv.data_ptr(), doc_start.data_ptr<int>(),
-                      doc_end.data_ptr<int>(), B, S, Hq, Hkv, D, (float)scale,
-                      cur_stream());
-  return {dq, dk, dv};
+  return attn_bwd_impl(dout, q, k, v, o, lse, doc_start, doc_end, scale);
 }
 
 }  // namespace

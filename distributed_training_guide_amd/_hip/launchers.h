@@ -101,24 +101,16 @@ void grad_sqsum_launch(const void* descs, int nchunks, float* partials,
 void grad_scale_launch(const void* descs, int nchunks, const float* sq_total,
                        float max_norm, hipStream_t s);
 
-// attention_fwd.hip, attention_bwd.hip
+// attention_fwd.hip, attention_bwd.hip.  doc_start / doc_end are the [B,S]
+// int32 tables of the document-masked mode for packed rows (first token /
+// exclusive end of each token's document); null selects the plain causal
+// kernels.  The backward takes both or neither.
 void attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
-                     float* lse, int B, int S, int Hq, int Hkv, int D,
-                     float scale, hipStream_t stream);
+                     float* lse, const int* doc_start, int B, int S, int Hq,
+                     int Hkv, int D, float scale, hipStream_t stream);
 void attn_bwd_launch(const void* dout, const void* q, const void* k,
                      const void* v, const void* o, const float* lse,
-                     float* delta, void* dq, void* dk, void* dv, int B, int S,
+                     float* delta, void* dq, void* dk, void* dv,
+                     const int* doc_start, const int* doc_end, int B, int S,
                      int Hq, int Hkv, int D, float scale, hipStream_t stream);
-// document-masked mode for packed rows: doc_start/doc_end are [B,S] int32
-// (first token / exclusive end of each token's document)
-void attn_fwd_doc_launch(const void* q, const void* k, const void* v, void* o,
-                         float* lse, const int* doc_start, int B, int S,
-                         int Hq, int Hkv, int D, float scale,
-                         hipStream_t stream);
-void attn_bwd_doc_launch(const void* dout, const void* q, const void* k,
-                         const void* v, const void* o, const float* lse,
-                         float* delta, void* dq, void* dk, void* dv,
-                         const int* doc_start, const int* doc_end, int B,
-                         int S, int Hq, int Hkv, int D, float scale,
-                         hipStream_t stream);
 }

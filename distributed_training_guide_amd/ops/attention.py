@@ -19,34 +19,25 @@ from .reference import attention_ref
 
 
 class _FlashAttnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, scale):
-        o, lse = ext().attn_fwd(q, k, v, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.scale = scale
-        return o
+    """doc_start / doc_end: the int32 [B,S] tables of a DocBounds, or both
+    None for plain causal attention."""
 
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, o, lse = ctx.saved_tensors
-        dq, dk, dv = ext().attn_bwd(dout.contiguous(), q, k, v, o, lse,
-                                    ctx.scale)
-        return dq, dk, dv, None
-
-
-class _FlashAttnDocFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, doc_start, doc_end, scale):
-        o, lse = ext().attn_fwd_doc(q, k, v, doc_start, scale)
-        ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
+        if doc_start is None:
+            o, lse = ext().attn_fwd(q, k, v, scale)
+            ctx.save_for_backward(q, k, v, o, lse)
+        else:
+            o, lse = ext().attn_fwd_doc(q, k, v, doc_start, scale)
+            ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
         ctx.scale = scale
         return o
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, o, lse, doc_start, doc_end = ctx.saved_tensors
-        dq, dk, dv = ext().attn_bwd_doc(dout.contiguous(), q, k, v, o, lse,
-                                        doc_start, doc_end, ctx.scale)
+        q, k, v, o, lse, *doc = ctx.saved_tensors
+        bwd = ext().attn_bwd_doc if doc else ext().attn_bwd
+        dq, dk, dv = bwd(dout.contiguous(), q, k, v, o, lse, *doc, ctx.scale)
         return dq, dk, dv, None, None, None
 
 
@@ -72,15 +63,12 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     table on every call."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if doc is None:
-        if use_hip(q, k, v):
-            return _FlashAttnFn.apply(q.contiguous(), k.contiguous(),
-                                      v.contiguous(), scale)
-        return attention_ref(q, k, v, scale)
-    doc = as_doc_bounds(doc)
-    _check_doc(doc, q)
+    start = end = None
+    if doc is not None:
+        doc = as_doc_bounds(doc)
+        _check_doc(doc, q)
+        start, end = doc.start.contiguous(), doc.end.contiguous()
     if use_hip(q, k, v):
-        return _FlashAttnDocFn.apply(q.contiguous(), k.contiguous(),
-                                     v.contiguous(), doc.start.contiguous(),
-                                     doc.end.contiguous(), scale)
-    return attention_ref(q, k, v, scale, doc.start)
+        return _FlashAttnFn.apply(q.contiguous(), k.contiguous(),
+                                  v.contiguous(), start, end, scale)
+    return attention_ref(q, k, v, scale, start)

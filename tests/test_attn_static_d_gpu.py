@@ -2,7 +2,8 @@
 instantiations) and their raw-exp2 softmax, against the fp32 reference.
 
 Small shapes at which a specialised kernel can go wrong: under one tile,
-ragged, several tiles with GQA; each with and without the document mask.
+ragged, several tiles with GQA, eight (batch, kv-head) groups of several
+blocks (the XCD-aware block remap); each with and without the document mask.
 Then the edges of the raw hardware exp2: scores of about +-200 (underflow to
 0, saturated rows) and a document layout whose 16-row groups meet fully
 masked diagonal tiles.
@@ -26,6 +27,11 @@ SHAPES = {
     "under_tile": (1, 48, 2, 2, [5, 43]),
     "ragged": (1, 200, 2, 2, [77, 123]),
     "tiles_gqa": (2, 256, 8, 2, [1, 62, 1, 70, 122]),
+    # B * Hkv = 8 groups with four forward / dq blocks (GQA 2 x 2 q tiles)
+    # and four dkdv blocks each: the XCD-aware remap takes its
+    # groups-divide-over-the-XCDs branch and is not the identity, so a wrong
+    # remap computes the wrong (b, h, tile)
+    "remap_xcd": (2, 256, 8, 4, [1, 62, 1, 70, 122]),
 }
 
 
@@ -151,3 +157,34 @@ def test_first_row_of_a_document_returns_its_value(doc):
     rows = [0] + ([_EDGE_LENS[0]] if doc else [])
     for r in rows:
         assert torch.equal(o[:, r], v[:, r]), r
+
+
+@pytest.mark.parametrize("doc", [False, True], ids=["causal", "doc"])
+def test_backward_bindings_reject_bad_inputs(doc):
+    """attn_bwd / attn_bwd_doc check their tensors like the forward does and
+    raise before any launch: a head dim without an instantiation, and a q
+    that is not contiguous."""
+    B, S, H = 1, 64, 2
+    start = _doc_start([S], B, S)
+    bounds = ops.doc_bounds(start)
+
+    def bwd(dout, q, k, v, o, lse):
+        if doc:
+            return ext().attn_bwd_doc(dout, q, k, v, o, lse, bounds.start,
+                                      bounds.end, 0.125)
+        return ext().attn_bwd(dout, q, k, v, o, lse, 0.125)
+
+    def inputs(D):
+        t = [torch.zeros(B, S, H, D, device="cuda", dtype=torch.bfloat16)
+             for _ in range(5)]
+        return t + [torch.zeros(B, H, S, device="cuda")]
+
+    with pytest.raises(RuntimeError, match="head dim must be 64 or 128"):
+        bwd(*inputs(96))
+    dout, q, k, v, o, lse = inputs(64)
+    q_nc = torch.zeros(B, S, 64, H, device="cuda",
+                       dtype=torch.bfloat16).transpose(2, 3)
+    assert q_nc.shape == q.shape and not q_nc.is_contiguous()
+    with pytest.raises(RuntimeError, match="q must be contiguous"):
+        bwd(dout, q_nc, k, v, o, lse)
+    torch.cuda.synchronize()
