@@ -18,6 +18,55 @@ inline hipStream_t cur_stream() {
   TORCH_CHECK((t).dtype() == torch::kBFloat16, #t " must be bf16");   \
   TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 
+// cos / sin rope tables: f32 [max_pos, D/2], on x's device, equal shapes
+#define CHECK_ROPE_TABLES(cos, sin, x, D)                                  \
+  TORCH_CHECK((D) % 2 == 0, "rope head dim must be even");                 \
+  TORCH_CHECK((cos).is_cuda() && (cos).device() == (x).device() &&         \
+                  (sin).is_cuda() && (sin).device() == (x).device(),       \
+              "rope tables must be on " #x "'s device");                   \
+  TORCH_CHECK((cos).dtype() == torch::kFloat &&                            \
+                  (sin).dtype() == torch::kFloat,                          \
+              "rope tables must be f32");                                  \
+  TORCH_CHECK((cos).is_contiguous() && (sin).is_contiguous(),              \
+              "rope tables must be contiguous");                           \
+  TORCH_CHECK((cos).dim() == 2 && (cos).size(1) == (D) / 2 &&              \
+                  (sin).sizes() == (cos).sizes(),                          \
+              "rope tables must both be [max_pos, D/2]")
+
+// optional int32 [S] absolute positions on x's device; without them the
+// table itself must cover the sequence
+inline const int* rope_positions(const c10::optional<torch::Tensor>& positions,
+                                 const torch::Tensor& cos,
+                                 const torch::Tensor& x, int64_t S) {
+  if (!positions.has_value()) {
+    TORCH_CHECK(cos.size(0) >= S, "rope table shorter than sequence");
+    return nullptr;
+  }
+  TORCH_CHECK(positions->is_cuda() && positions->device() == x.device(),
+              "positions must be on the input's device");
+  TORCH_CHECK(positions->dtype() == torch::kInt && positions->is_contiguous(),
+              "positions must be contiguous int32");
+  TORCH_CHECK(positions->numel() == S, "positions must be [S]");
+  return positions->data_ptr<int>();
+}
+
+// what every cross-entropy entry point requires of logits / labels / S_out
+#define CHECK_CE_INPUTS(logits, labels, S_out)                             \
+  CHECK_BF16_CONTIG(logits);                                               \
+  TORCH_CHECK((logits).dim() == 3, "logits must be [B,S,V]");              \
+  TORCH_CHECK((labels).is_cuda() && (labels).device() == (logits).device(),\
+              "labels must be on the logits' device");                     \
+  TORCH_CHECK((labels).dtype() == torch::kLong && (labels).is_contiguous(),\
+              "labels must be contiguous int64");                          \
+  TORCH_CHECK((labels).dim() == 2 &&                                       \
+                  (labels).size(0) == (logits).size(0) &&                  \
+                  (labels).size(1) == (logits).size(1),                    \
+              "labels must be [B,S]");                                     \
+  TORCH_CHECK((S_out) > 0 && (S_out) <= (logits).size(1),                  \
+              "S_out must be in (0, S]");                                  \
+  TORCH_CHECK((logits).size(2) % 8 == 0,                                   \
+              "vocab must be padded to a multiple of 8")
+
 // [nblocks, H] f32 per-block partials of a norm backward, plus the
 // COLSUM_RY tail rows colsum_launch folds them through
 inline torch::Tensor alloc_partials(int nblocks, int H,
@@ -63,16 +112,8 @@ torch::Tensor rope(torch::Tensor x, torch::Tensor cos, torch::Tensor sin,
   CHECK_BF16_CONTIG(x);
   TORCH_CHECK(x.dim() == 4, "rope expects [B,S,H,D]");
   const int S = (int)x.size(1), H = (int)x.size(2), D = (int)x.size(3);
-  TORCH_CHECK(cos.is_contiguous() && sin.is_contiguous());
-  TORCH_CHECK(cos.dtype() == torch::kFloat);
-  const int* pos_ptr = nullptr;
-  if (positions.has_value()) {
-    TORCH_CHECK(positions->dtype() == torch::kInt && positions->is_contiguous());
-    TORCH_CHECK(positions->numel() == S, "positions must be [S]");
-    pos_ptr = positions->data_ptr<int>();
-  } else {
-    TORCH_CHECK(cos.size(0) >= S, "rope table shorter than sequence");
-  }
+  CHECK_ROPE_TABLES(cos, sin, x, D);
+  const int* pos_ptr = rope_positions(positions, cos, x, S);
   auto y = torch::empty_like(x);
   rope_launch(x.data_ptr(), y.data_ptr(), cos.data_ptr<float>(),
               sin.data_ptr<float>(), pos_ptr, x.numel() / D, S, H, D,
@@ -132,14 +173,8 @@ std::vector<torch::Tensor> qkv_rope_fwd(torch::Tensor qkv, torch::Tensor cos,
   TORCH_CHECK(D % 16 == 0,
               "qkv_rope requires head_dim % 16 == 0 (8-pair vectorized "
               "kernel); use the unfused rope path otherwise");
-  const int* pos_ptr = nullptr;
-  if (positions.has_value()) {
-    TORCH_CHECK(positions->dtype() == torch::kInt &&
-                positions->is_contiguous() && positions->numel() == S);
-    pos_ptr = positions->data_ptr<int>();
-  } else {
-    TORCH_CHECK(cos.size(0) >= S, "rope table shorter than sequence");
-  }
+  CHECK_ROPE_TABLES(cos, sin, qkv, D);
+  const int* pos_ptr = rope_positions(positions, cos, qkv, S);
   auto q = torch::empty({B, S, Hq, D}, qkv.options());
   auto k = torch::empty({B, S, Hkv, D}, qkv.options());
   auto v = torch::empty({B, S, Hkv, D}, qkv.options());
@@ -157,11 +192,18 @@ torch::Tensor qkv_rope_bwd(torch::Tensor dq, torch::Tensor dk,
   CHECK_BF16_CONTIG(dq);
   CHECK_BF16_CONTIG(dk);
   CHECK_BF16_CONTIG(dv);
+  TORCH_CHECK(dq.dim() == 4, "dq must be [B,S,Hq,D]");
+  TORCH_CHECK(dk.dim() == 4 && dk.size(0) == dq.size(0) &&
+                  dk.size(1) == dq.size(1) && dk.size(3) == dq.size(3),
+              "dk must be [B,S,Hkv,D]");
+  TORCH_CHECK(dv.sizes() == dk.sizes(), "dv must be [B,S,Hkv,D]");
+  TORCH_CHECK(dk.device() == dq.device() && dv.device() == dq.device(),
+              "dk and dv must be on dq's device");
   const int64_t B = dq.size(0), S = dq.size(1);
   const int64_t Hq = dq.size(2), Hkv = dk.size(2), D = dq.size(3);
   TORCH_CHECK(D % 16 == 0, "qkv_rope requires head_dim % 16 == 0");
-  const int* pos_ptr = nullptr;
-  if (positions.has_value()) pos_ptr = positions->data_ptr<int>();
+  CHECK_ROPE_TABLES(cos, sin, dq, D);
+  const int* pos_ptr = rope_positions(positions, cos, dq, S);
   auto dqkv = torch::empty({B, S, (Hq + 2 * Hkv) * D}, dq.options());
   qkv_rope_bwd_launch(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
                       dqkv.data_ptr(), cos.data_ptr<float>(),
@@ -188,7 +230,13 @@ torch::Tensor silu_mul_bwd(torch::Tensor dy, torch::Tensor gu) {
   CHECK_BF16_CONTIG(dy);
   CHECK_BF16_CONTIG(gu);
   const int I2 = (int)gu.size(-1);
+  TORCH_CHECK(I2 % 16 == 0, "packed gate_up dim must be a multiple of 16");
   const int I = I2 / 2;
+  auto sizes = gu.sizes().vec();
+  sizes.back() = I;
+  TORCH_CHECK(dy.sizes() == c10::IntArrayRef(sizes),
+              "dy must have gu's shape with the last dim halved");
+  TORCH_CHECK(dy.device() == gu.device(), "dy must be on gu's device");
   auto dgu = torch::empty_like(gu);
   silu_mul_bwd_launch(dy.data_ptr(), gu.data_ptr(), dgu.data_ptr(),
                       gu.numel() / I2, I, cur_stream());
@@ -198,6 +246,9 @@ torch::Tensor silu_mul_bwd(torch::Tensor dy, torch::Tensor gu) {
 // ---------------- embedding ----------------
 torch::Tensor embedding_fwd(torch::Tensor table, torch::Tensor ids) {
   CHECK_BF16_CONTIG(table);
+  TORCH_CHECK(table.dim() == 2, "table must be [V,H]");
+  TORCH_CHECK(ids.is_cuda() && ids.device() == table.device(),
+              "ids must be on the table's device");
   TORCH_CHECK(ids.dtype() == torch::kLong && ids.is_contiguous());
   const int64_t V = table.size(0);
   const int H = (int)table.size(1);
@@ -211,7 +262,10 @@ torch::Tensor embedding_fwd(torch::Tensor table, torch::Tensor ids) {
 
 torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor ids, int64_t V) {
   CHECK_BF16_CONTIG(dy);
+  TORCH_CHECK(ids.is_cuda() && ids.device() == dy.device(),
+              "ids must be on dy's device");
   TORCH_CHECK(ids.dtype() == torch::kLong && ids.is_contiguous());
+  TORCH_CHECK(dy.dim() >= 1 && V > 0, "dy must be [..., H] and V positive");
   const int H = (int)dy.size(-1);
   TORCH_CHECK(dy.numel() == ids.numel() * H, "dy/ids shape mismatch");
   auto acc = torch::empty({V, (int64_t)H},
@@ -273,6 +327,9 @@ torch::Tensor gelu_fwd(torch::Tensor x) {
 torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
   CHECK_BF16_CONTIG(dy);
   CHECK_BF16_CONTIG(x);
+  TORCH_CHECK(dy.numel() == x.numel(), "gelu_bwd: dy/x numel mismatch");
+  TORCH_CHECK(dy.device() == x.device(), "dy must be on x's device");
+  TORCH_CHECK(x.numel() % 8 == 0, "gelu kernel needs numel % 8 == 0");
   auto dx = torch::empty_like(x);
   gelu_bwd_launch(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(),
                   cur_stream());
@@ -282,12 +339,9 @@ torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
 // ---------------- cross entropy ----------------
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels,
                                   int64_t S_out, int64_t ignore_index) {
-  CHECK_BF16_CONTIG(logits);
-  TORCH_CHECK(labels.dtype() == torch::kLong && labels.is_contiguous());
-  TORCH_CHECK(logits.dim() == 3, "logits must be [B,S,V]");
+  CHECK_CE_INPUTS(logits, labels, S_out);
   const int B = (int)logits.size(0), S = (int)logits.size(1),
             V = (int)logits.size(2);
-  TORCH_CHECK(V % 8 == 0, "vocab must be padded to a multiple of 8");
   const int64_t nrows = (int64_t)B * S_out;
   auto loss = torch::empty({nrows}, logits.options().dtype(torch::kFloat));
   auto lse = torch::empty({nrows}, logits.options().dtype(torch::kFloat));
@@ -301,7 +355,7 @@ std::vector<torch::Tensor> ce_fwd_sharded(torch::Tensor logits,
                                           torch::Tensor labels, int64_t S_out,
                                           int64_t vocab_start,
                                           int64_t ignore_index) {
-  CHECK_BF16_CONTIG(logits);
+  CHECK_CE_INPUTS(logits, labels, S_out);
   const int B = (int)logits.size(0), S = (int)logits.size(1),
             V = (int)logits.size(2);
   const int64_t nrows = (int64_t)B * S_out;
@@ -320,10 +374,14 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor labels,
                      torch::Tensor lse, double scale, int64_t S_out,
                      int64_t vocab_start, int64_t ignore_index, bool sharded,
                      c10::optional<torch::Tensor> scale_t = c10::nullopt) {
-  CHECK_BF16_CONTIG(logits);
+  CHECK_CE_INPUTS(logits, labels, S_out);
   const int B = (int)logits.size(0), S = (int)logits.size(1),
             V = (int)logits.size(2);
   const int64_t nrows = (int64_t)B * S_out;
+  TORCH_CHECK(lse.is_cuda() && lse.device() == logits.device() &&
+                  lse.dtype() == torch::kFloat && lse.is_contiguous() &&
+                  lse.numel() == nrows,
+              "lse must be a contiguous f32 [B*S_out] on the logits' device");
   const float* sp = nullptr;
   if (scale_t.has_value()) {
     TORCH_CHECK(scale_t->dtype() == torch::kFloat && scale_t->is_cuda() &&

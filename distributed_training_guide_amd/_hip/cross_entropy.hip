@@ -42,6 +42,9 @@ __global__ void __launch_bounds__(256) ce_fwd_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float f = bf2f(v[j]);
+        // a -inf logit (masked column, padding of the tail vector) adds 0
+        // whatever m is; with m still -inf, f - m would be NaN
+        if (f == -INFINITY) continue;
         if (f > m) { sum *= __expf(m - f); m = f; }
         sum += __expf(f - m);
       }

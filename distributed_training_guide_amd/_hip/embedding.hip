@@ -93,7 +93,8 @@ void embed_bwd_launch(const void* dy, const int64_t* ids, float* acc,
                      (const short*)dy, ids, acc, nrows, H, V);
   int64_t n = V * (int64_t)H;
   int64_t cblocks = (n / 4 + 255) / 256;
-  int cgrid = (int)(cblocks < 8192 ? cblocks : 8192);
+  // never an empty grid: V*H < 4 is all tail
+  int cgrid = (int)(cblocks < 1 ? 1 : cblocks < 8192 ? cblocks : 8192);
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(cgrid), dim3(256), 0, s,
                      acc, (short*)dtable, n);
 }

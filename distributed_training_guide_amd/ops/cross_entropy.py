@@ -94,7 +94,8 @@ def sharded_causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,
                                         group)
     # CPU (gloo) reference path for tests: all-gather the shards and use the
     # eager loss. Differentiable through all_gather is not needed on CPU
-    # tests of the loss value; gradient path tested on GPU.
+    # tests of the loss value; the gradient path is tested on the GPU
+    # (tests/test_ce_sharded_gpu.py).
     world = dist.get_world_size(group)
     shards = [torch.empty_like(logits) for _ in range(world)]
     dist.all_gather(shards, logits.contiguous(), group=group)

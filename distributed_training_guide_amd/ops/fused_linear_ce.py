@@ -59,7 +59,8 @@ class _FusedLinearCEFn(torch.autograd.Function):
         logits = None
         if keep_logits:
             logits = torch.matmul(x2, weight.t())  # [N,V], saved
-            loss_rows, lse = ext().ce_fwd(logits.unsqueeze(0), shifted, N,
+            loss_rows, lse = ext().ce_fwd(logits.unsqueeze(0),
+                                          shifted.unsqueeze(0), N,
                                           IGNORE_INDEX)
             loss_sum = loss_rows.sum()
         else:
@@ -70,7 +71,7 @@ class _FusedLinearCEFn(torch.autograd.Function):
                 r1 = min(r0 + chunk_rows, N)
                 logits_c = torch.matmul(x2[r0:r1], wt)  # transient
                 lc, lse_c = ext().ce_fwd(logits_c.unsqueeze(0),
-                                         shifted[r0:r1], r1 - r0,
+                                         shifted[r0:r1].unsqueeze(0), r1 - r0,
                                          IGNORE_INDEX)
                 loss_sum += lc.sum()
                 lse[r0:r1] = lse_c
@@ -108,7 +109,8 @@ class _FusedLinearCEFn(torch.autograd.Function):
             L = r1 - r0
             logits_c = (logits[r0:r1] if logits is not None
                         else torch.matmul(x2[r0:r1], wt))  # recompute
-            dlogits_c = ext().ce_bwd(logits_c.unsqueeze(0), shifted[r0:r1],
+            dlogits_c = ext().ce_bwd(logits_c.unsqueeze(0),
+                                     shifted[r0:r1].unsqueeze(0),
                                      lse[r0:r1], 0.0, L, 0, IGNORE_INDEX,
                                      False, scale_t).squeeze(0)
             del logits_c
