@@ -2,6 +2,7 @@
 // linked against libtorch; no hipify, no CUDA compatibility layer —
 // c10::hip is the native ROCm stream API).
 #include <torch/extension.h>
+#include <c10/hip/HIPException.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
@@ -75,35 +76,151 @@ inline torch::Tensor alloc_partials(int nblocks, int H,
                       like.options().dtype(torch::kFloat));
 }
 
-// ---------------- rmsnorm ----------------
-std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
-                                       double eps) {
+// ---------------- norms (norm.hip) ----------------
+struct NormDims {
+  int64_t nrows;
+  int H;
+};
+
+// What every norm entry point requires before it launches.  x is the
+// [..., H] input; `wb` the weight (and LayerNorm's bias), each exactly [H];
+// `like_x` the tensors that travel with x (dy, dres_out, delta): x's sizes;
+// `stats` the saved rstd (and mu): f32, one value per row.  All on x's device.
+NormDims norm_check(const torch::Tensor& x,
+                    std::initializer_list<torch::Tensor> wb,
+                    std::initializer_list<torch::Tensor> like_x = {},
+                    std::initializer_list<torch::Tensor> stats = {}) {
   CHECK_BF16_CONTIG(x);
-  CHECK_BF16_CONTIG(w);
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0,
+              "norm input must be [..., H] with H > 0");
   const int H = (int)x.size(-1);
   const int64_t nrows = x.numel() / H;
+  for (const auto& weight_or_bias : wb) {
+    CHECK_BF16_CONTIG(weight_or_bias);
+    TORCH_CHECK(weight_or_bias.dim() == 1 && weight_or_bias.size(0) == H &&
+                    weight_or_bias.device() == x.device(),
+                "norm weight / bias must be [H] on the input's device");
+  }
+  for (const auto& dy_or_residual : like_x) {
+    CHECK_BF16_CONTIG(dy_or_residual);
+    TORCH_CHECK(dy_or_residual.sizes() == x.sizes() &&
+                    dy_or_residual.device() == x.device(),
+                "norm: dy / dres_out / delta must have the input's sizes "
+                "and device");
+  }
+  for (const auto& t : stats) {
+    TORCH_CHECK(t.is_cuda() && t.device() == x.device(),
+                "norm: rstd / mu must be on the input's device");
+    TORCH_CHECK(t.dtype() == torch::kFloat && t.is_contiguous(),
+                "norm: rstd / mu must be contiguous f32");
+    TORCH_CHECK(t.numel() == nrows,
+                "norm: rstd / mu must hold one value per row");
+  }
+  return {nrows, H};
+}
+
+// the fused residual kernels are vector-only and stage a row in LDS
+inline void add_rmsnorm_check_H(int H) {
+  TORCH_CHECK(H % 8 == 0 && H <= 16384, "add_rmsnorm: unsupported H");
+}
+
+inline int norm_bwd_blocks(int64_t nrows) {
+  return (int)std::min<int64_t>(nrows, 2048);
+}
+
+std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
+                                       double eps) {
+  const NormDims d = norm_check(x, {w});
   auto y = torch::empty_like(x);
-  auto rstd = torch::empty({nrows}, x.options().dtype(torch::kFloat));
-  rmsnorm_fwd_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(), rstd.data_ptr(),
-                     nrows, H, (float)eps, cur_stream());
+  auto rstd = torch::empty({d.nrows}, x.options().dtype(torch::kFloat));
+  norm_fwd_launch(x.data_ptr(), w.data_ptr(), nullptr, y.data_ptr(), nullptr,
+                  rstd.data_ptr<float>(), d.nrows, d.H, (float)eps,
+                  cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {y, rstd};
 }
 
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        torch::Tensor w, torch::Tensor rstd) {
-  CHECK_BF16_CONTIG(dy);
-  CHECK_BF16_CONTIG(x);
-  const int H = (int)x.size(-1);
-  const int64_t nrows = x.numel() / H;
-  const int nblocks = (int)std::min<int64_t>(nrows, 2048);
+  const NormDims d = norm_check(x, {w}, {dy}, {rstd});
+  const int nblocks = norm_bwd_blocks(d.nrows);
   auto dx = torch::empty_like(x);
   auto dw = torch::empty_like(w);
-  auto dw_partial = alloc_partials(nblocks, H, x);
-  rmsnorm_bwd_launch(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
-                     rstd.data_ptr(), dx.data_ptr(),
-                     dw_partial.data_ptr<float>(), dw.data_ptr(), nblocks,
-                     nrows, H, cur_stream());
+  auto dw_partial = alloc_partials(nblocks, d.H, x);
+  norm_bwd_launch(dy.data_ptr(), nullptr, x.data_ptr(), w.data_ptr(), nullptr,
+                  rstd.data_ptr<float>(), dx.data_ptr(),
+                  dw_partial.data_ptr<float>(), nullptr, dw.data_ptr(),
+                  nullptr, nblocks, d.nrows, d.H, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dx, dw};
+}
+
+std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor res,
+                                           torch::Tensor delta,
+                                           torch::Tensor w, double eps) {
+  const NormDims d = norm_check(res, {w}, {delta});
+  add_rmsnorm_check_H(d.H);
+  auto res_out = torch::empty_like(res);
+  auto y = torch::empty_like(res);
+  auto rstd = torch::empty({d.nrows}, res.options().dtype(torch::kFloat));
+  add_rmsnorm_fwd_launch(res.data_ptr(), delta.data_ptr(), w.data_ptr(),
+                         res_out.data_ptr(), y.data_ptr(), rstd.data_ptr(),
+                         d.nrows, d.H, (float)eps, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {y, res_out, rstd};
+}
+
+std::vector<torch::Tensor> add_rmsnorm_bwd(torch::Tensor dy,
+                                           torch::Tensor dres_out,
+                                           torch::Tensor res_out,
+                                           torch::Tensor w,
+                                           torch::Tensor rstd) {
+  const NormDims d = norm_check(res_out, {w}, {dy, dres_out}, {rstd});
+  add_rmsnorm_check_H(d.H);
+  const int nblocks = norm_bwd_blocks(d.nrows);
+  auto dx = torch::empty_like(res_out);
+  auto dw = torch::empty_like(w);
+  auto dw_partial = alloc_partials(nblocks, d.H, res_out);
+  norm_bwd_launch(dy.data_ptr(), dres_out.data_ptr(), res_out.data_ptr(),
+                  w.data_ptr(), nullptr, rstd.data_ptr<float>(),
+                  dx.data_ptr(), dw_partial.data_ptr<float>(), nullptr,
+                  dw.data_ptr(), nullptr, nblocks, d.nrows, d.H,
+                  cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {dx, dw};
+}
+
+std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
+                                         torch::Tensor b, double eps) {
+  const NormDims d = norm_check(x, {w, b});
+  auto y = torch::empty_like(x);
+  auto opts = x.options().dtype(torch::kFloat);
+  auto mu = torch::empty({d.nrows}, opts);
+  auto rstd = torch::empty({d.nrows}, opts);
+  norm_fwd_launch(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(),
+                  mu.data_ptr<float>(), rstd.data_ptr<float>(), d.nrows, d.H,
+                  (float)eps, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {y, mu, rstd};
+}
+
+std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                         torch::Tensor w, torch::Tensor mu,
+                                         torch::Tensor rstd) {
+  const NormDims d = norm_check(x, {w}, {dy}, {mu, rstd});
+  const int nblocks = norm_bwd_blocks(d.nrows);
+  auto dx = torch::empty_like(x);
+  auto dw = torch::empty_like(w);
+  auto db = torch::empty_like(w);
+  auto dw_partial = alloc_partials(nblocks, d.H, x);
+  auto db_partial = alloc_partials(nblocks, d.H, x);
+  norm_bwd_launch(dy.data_ptr(), nullptr, x.data_ptr(), w.data_ptr(),
+                  mu.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(),
+                  dw_partial.data_ptr<float>(), db_partial.data_ptr<float>(),
+                  dw.data_ptr(), db.data_ptr(), nblocks, d.nrows, d.H,
+                  cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {dx, dw, db};
 }
 
 // ---------------- rope ----------------
@@ -119,46 +236,6 @@ torch::Tensor rope(torch::Tensor x, torch::Tensor cos, torch::Tensor sin,
               sin.data_ptr<float>(), pos_ptr, x.numel() / D, S, H, D,
               backward ? 1 : 0, cur_stream());
   return y;
-}
-
-// ---------------- fused residual add + rmsnorm ----------------
-std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor res,
-                                           torch::Tensor delta,
-                                           torch::Tensor w, double eps) {
-  CHECK_BF16_CONTIG(res);
-  CHECK_BF16_CONTIG(delta);
-  CHECK_BF16_CONTIG(w);
-  const int H = (int)res.size(-1);
-  TORCH_CHECK(H % 8 == 0 && H <= 16384, "add_rmsnorm: unsupported H");
-  const int64_t nrows = res.numel() / H;
-  auto res_out = torch::empty_like(res);
-  auto y = torch::empty_like(res);
-  auto rstd = torch::empty({nrows}, res.options().dtype(torch::kFloat));
-  add_rmsnorm_fwd_launch(res.data_ptr(), delta.data_ptr(), w.data_ptr(),
-                         res_out.data_ptr(), y.data_ptr(), rstd.data_ptr(),
-                         nrows, H, (float)eps, cur_stream());
-  return {y, res_out, rstd};
-}
-
-std::vector<torch::Tensor> add_rmsnorm_bwd(torch::Tensor dy,
-                                           torch::Tensor dres_out,
-                                           torch::Tensor res_out,
-                                           torch::Tensor w,
-                                           torch::Tensor rstd) {
-  CHECK_BF16_CONTIG(dy);
-  CHECK_BF16_CONTIG(dres_out);
-  CHECK_BF16_CONTIG(res_out);
-  const int H = (int)res_out.size(-1);
-  const int64_t nrows = res_out.numel() / H;
-  const int nblocks = (int)std::min<int64_t>(nrows, 2048);
-  auto dx = torch::empty_like(res_out);
-  auto dw = torch::empty_like(w);
-  auto dw_partial = alloc_partials(nblocks, H, res_out);
-  add_rmsnorm_bwd_launch(dy.data_ptr(), dres_out.data_ptr(),
-                         res_out.data_ptr(), w.data_ptr(), rstd.data_ptr(),
-                         dx.data_ptr(), dw_partial.data_ptr<float>(),
-                         dw.data_ptr(), nblocks, nrows, H, cur_stream());
-  return {dx, dw};
 }
 
 // ---------------- fused qkv split + rope ----------------
@@ -277,45 +354,7 @@ torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor ids, int64_t V) {
   return dtable;
 }
 
-// ---------------- layernorm + gelu (GPT-2 ops) ----------------
-std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
-                                         torch::Tensor b, double eps) {
-  CHECK_BF16_CONTIG(x);
-  CHECK_BF16_CONTIG(w);
-  CHECK_BF16_CONTIG(b);
-  const int H = (int)x.size(-1);
-  const int64_t nrows = x.numel() / H;
-  auto y = torch::empty_like(x);
-  auto opts = x.options().dtype(torch::kFloat);
-  auto mu = torch::empty({nrows}, opts);
-  auto rstd = torch::empty({nrows}, opts);
-  ln_fwd_launch(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(),
-                mu.data_ptr<float>(), rstd.data_ptr<float>(), nrows, H,
-                (float)eps, cur_stream());
-  return {y, mu, rstd};
-}
-
-std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                         torch::Tensor w, torch::Tensor mu,
-                                         torch::Tensor rstd) {
-  CHECK_BF16_CONTIG(dy);
-  CHECK_BF16_CONTIG(x);
-  const int H = (int)x.size(-1);
-  const int64_t nrows = x.numel() / H;
-  const int nblocks = (int)std::min<int64_t>(nrows, 2048);
-  auto dx = torch::empty_like(x);
-  auto dw = torch::empty_like(w);
-  auto db = torch::empty_like(w);
-  auto dw_partial = alloc_partials(nblocks, H, x);
-  auto db_partial = alloc_partials(nblocks, H, x);
-  ln_bwd_launch(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
-                mu.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(),
-                dw_partial.data_ptr<float>(), db_partial.data_ptr<float>(),
-                dw.data_ptr(), db.data_ptr(), nblocks, nrows, H,
-                cur_stream());
-  return {dx, dw, db};
-}
-
+// ---------------- gelu (GPT-2 MLP) ----------------
 torch::Tensor gelu_fwd(torch::Tensor x) {
   CHECK_BF16_CONTIG(x);
   TORCH_CHECK(x.numel() % 8 == 0, "gelu kernel needs numel % 8 == 0");

@@ -1,6 +1,6 @@
 // Column sum of f32 partials for gfx950: partial [nblocks, H] -> out [H] bf16.
 //
-// The norm backward kernels (rmsnorm.hip, layernorm.hip) leave one row of
+// The norm backward kernels (norm.hip) leave one row of
 // weight/bias-gradient partials per block; this finishes the reduction.
 // Two stages so the read of the (up to 2048 x H) buffer parallelizes over
 // enough blocks to reach memory bandwidth (a single H/256-block pass is

@@ -19,30 +19,26 @@ extern "C" {
 void colsum_launch(float* partial, void* out, int nblocks, int H,
                    hipStream_t s);
 
-// rmsnorm.hip
-void rmsnorm_fwd_launch(const void* x, const void* w, void* y, void* rstd,
-                        int64_t nrows, int H, float eps, hipStream_t s);
-void rmsnorm_bwd_launch(const void* dy, const void* x, const void* w,
-                        const void* rstd, void* dx, float* dw_partial,
-                        void* dw, int nblocks, int64_t nrows, int H,
-                        hipStream_t s);
+// norm.hip.  One forward and one backward entry point serve RMSNorm and
+// LayerNorm: a null `mu` (and `b`) selects RMSNorm, otherwise LayerNorm.  In
+// the backward a non-null `dres` selects RMSNorm's fused residual form,
+// dx += dres (H % 8 == 0 and H <= 16384 only; LayerNorm has none, so `dres`
+// is null whenever `mu` is not).  `db_partial` / `db` are LayerNorm's and
+// null for RMSNorm.  With nblocks == 0 (no rows) the backward launches no
+// norm kernel and dw (db) come out as zeros.
+void norm_fwd_launch(const void* x, const void* w, const void* b, void* y,
+                     float* mu, float* rstd, int64_t nrows, int H, float eps,
+                     hipStream_t s);
 void add_rmsnorm_fwd_launch(const void* res, const void* delta, const void* w,
                             void* res_out, void* y, void* rstd, int64_t nrows,
                             int H, float eps, hipStream_t s);
-void add_rmsnorm_bwd_launch(const void* dy, const void* dres_out,
-                            const void* x, const void* w, const void* rstd,
-                            void* dx, float* dw_partial, void* dw,
-                            int nblocks, int64_t nrows, int H,
-                            hipStream_t s);
+void norm_bwd_launch(const void* dy, const void* dres, const void* x,
+                     const void* w, const float* mu, const float* rstd,
+                     void* dx, float* dw_partial, float* db_partial, void* dw,
+                     void* db, int nblocks, int64_t nrows, int H,
+                     hipStream_t s);
 
-// layernorm.hip
-void ln_fwd_launch(const void* x, const void* w, const void* b, void* y,
-                   float* mu, float* rstd, int64_t nrows, int H, float eps,
-                   hipStream_t s);
-void ln_bwd_launch(const void* dy, const void* x, const void* w,
-                   const float* mu, const float* rstd, void* dx,
-                   float* dw_partial, float* db_partial, void* dw, void* db,
-                   int nblocks, int64_t nrows, int H, hipStream_t s);
+// gelu.hip
 void gelu_fwd_launch(const void* x, void* y, int64_t n, hipStream_t s);
 void gelu_bwd_launch(const void* dy, const void* x, void* dx, int64_t n,
                      hipStream_t s);

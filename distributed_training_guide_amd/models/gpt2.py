@@ -4,7 +4,7 @@
 Learned positional embeddings, pre-LayerNorm blocks, GELU MLP, tied
 embeddings — config-compatible shapes with HF gpt2.  Fully on the in-repo
 gfx950 kernels: the flash attention kernel (head_dim 64), fused LayerNorm
-and tanh-GELU (layernorm.hip) and the fused lm_head+CE loss.
+and tanh-GELU (norm.hip, gelu.hip) and the fused lm_head+CE loss.
 """
 from dataclasses import dataclass, field
 

@@ -211,7 +211,7 @@ class LlamaForCausalLM(nn.Module):
         x = self.embed_tokens(input_ids)
         if x.is_cuda:
             # fused (delta, residual) path: every residual add is fused
-            # into the next RMSNorm kernel (rmsnorm.hip). Every layer
+            # into the next RMSNorm kernel (norm.hip). Every layer
             # is entered through __call__ so FSDP / activation-checkpoint
             # hooks fire; the zero first delta costs one extra H-read.
             residual = x

@@ -1,4 +1,4 @@
-"""LayerNorm + tanh-GELU ops: HIP kernels on GPU (layernorm.hip), eager
+"""LayerNorm + tanh-GELU ops: HIP kernels on GPU (norm.hip, gelu.hip), eager
 fp32 reference on CPU — the GPT-2 block's norm/activation, so chapter-1's
 smoke model (reference 01-single-gpu/README.md:9-12 trains HF gpt2) runs
 fully on the in-repo HIP path like the Llama chapters."""

@@ -1,4 +1,4 @@
-"""RMSNorm op: HIP kernel on GPU (rmsnorm.hip), eager fp32 reference on CPU.
+"""RMSNorm op: HIP kernel on GPU (norm.hip), eager fp32 reference on CPU.
 
 Replaces transformers' LlamaRMSNorm in the reference model stack
 (/root/reference/04-fully-sharded-data-parallel/train_llm.py:32-44 patches
@@ -52,7 +52,7 @@ class RMSNorm(torch.nn.Module):
 
 
 class _AddRMSNormFn(torch.autograd.Function):
-    """Fused residual-add + RMSNorm (rmsnorm.hip): res_out = res+delta,
+    """Fused residual-add + RMSNorm (norm.hip): res_out = res+delta,
     y = rmsnorm(res_out)*w in one pass; backward folds the downstream
     residual gradient into dx (no separate elementwise adds)."""
 

@@ -1,5 +1,5 @@
 """GPT-2 HIP op numerics vs plain PyTorch fp32 references: LayerNorm
-fwd/bwd (incl. dw/db reductions) and tanh-GELU fwd/bwd (layernorm.hip)."""
+fwd/bwd (incl. dw/db reductions; norm.hip) and tanh-GELU fwd/bwd (gelu.hip)."""
 import pytest
 import torch
 
@@ -10,6 +10,9 @@ pytestmark = pytest.mark.gpu
     (512, 768), (1000, 1600), (64, 104),
     (3, 100),    # H % 8 != 0: scalar path
     (2100, 64),  # > 2048 rows: a block folds two rows into one partial
+    (5, 2056),   # two register chunks, the second is one thread's 8 columns
+    (3, 4104),   # NCH = 4: chunk 3 is one thread, chunk 4 is empty
+    (2, 8192),   # last H on the vector path, all four chunks full
     (2, 8200),   # H > 8192: past the register accumulators, scalar fallback
 ])
 def test_layernorm_matches_fp32(rows, H):

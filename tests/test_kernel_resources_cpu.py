@@ -3,7 +3,7 @@
 The norm kernels keep their accumulators in registers by design; scratch in
 any of them means the compiler moved an array to private memory (a run-time
 index into it does that), which no test of results can see.  Needs hipcc,
-not a GPU; compiles rmsnorm.hip for the device only (a few seconds)."""
+not a GPU; compiles norm.hip for the device only (a few seconds)."""
 import shutil
 import sys
 from pathlib import Path
@@ -33,13 +33,19 @@ a.hip:27:1: remark:     LDS Size [bytes/block]: 32 [-Rpass-analysis=kernel-resou
 
 
 @needs_hipcc
-def test_rmsnorm_kernels_use_no_scratch():
-    rows = kernel_resources.analyze(
-        kernel_resources.HIP_DIR / "rmsnorm.hip")
+def test_norm_kernels_use_no_scratch():
+    rows = kernel_resources.analyze(kernel_resources.HIP_DIR / "norm.hip")
     names = [r["name"] for r in rows]
     print(*rows, sep="\n")
-    # forward, fused forward, and the backward per (residual, chunk count)
-    assert sum("rmsnorm_bwd_kernel" in n for n in names) == 8, names
+    # backward per (residual, chunk count) for RMSNorm and per chunk count
+    # for LayerNorm; both forwards and the fused forward
+    bwd = [n for n in names if "norm_bwd_kernel" in n]
+    assert sum(n.startswith("norm_bwd_kernel<false,") for n in bwd) == 8, names
+    assert sorted(n for n in bwd if n.startswith("norm_bwd_kernel<true,")) \
+        == [f"norm_bwd_kernel<true, false, {c}>" for c in (1, 2, 4)], names
+    assert len(bwd) == 11, names
+    assert sorted(n for n in names if "norm_fwd_kernel<" in n) == [
+        "norm_fwd_kernel<false>", "norm_fwd_kernel<true>"], names
     assert any("add_rmsnorm_fwd_kernel" in n for n in names), names
     for r in rows:
         assert r["scratch"] == 0, r

@@ -1,6 +1,7 @@
-"""RMSNorm backward at the hidden sizes that select each register-chunk
-instantiation of rmsnorm_bwd_kernel (H / 2048 = 2, 4, 8) and at more rows
-than the grid has blocks, plain and fused with the residual add.
+"""Norm backward (norm.hip) at the hidden sizes that select each
+register-chunk instantiation of norm_bwd_kernel (H / 2048 = 2, 4, 8 for
+RMSNorm, plain and fused with the residual add; 1, 2, 4 and the scalar
+fallback for LayerNorm) and at more rows than the grid has blocks.
 
 Bounds are those of tests/test_ops_gpu.py (relative Frobenius error 3e-2).
 dw comes from per-block partials folded in a fixed order, with no atomics:
@@ -81,3 +82,44 @@ def test_add_rmsnorm_bwd(shape):
     assert torch.equal(dw1, dw2)
     assert torch.equal(dx1, dx2)
     assert torch.equal(dw1, w.grad)
+
+
+# H = 2056 / 4104: the last occupied chunk is one thread's 8 columns (and
+# the fourth chunk of 4104 is empty); 8192: the last H on the vector path;
+# 8200: the scalar fallback; 768 at 2100 rows: a block folds several rows.
+LN_SHAPES = [(5, 2056), (3, 4104), (2, 8192), (2100, 768), (2, 8200)]
+
+
+@pytest.mark.parametrize("shape", LN_SHAPES)
+def test_layernorm_bwd_chunks(shape):
+    """dx, dw and db against F.layer_norm in f32 on the same bf16 inputs,
+    each 2048-column chunk on its own so that an error confined to one
+    chunk is not diluted by the others.  The outputs are bf16, so the
+    expected error is one rounding (about 4e-3); the bound is the norm
+    backward bound used throughout (3e-2)."""
+    H = shape[-1]
+    x = _rand(shape, 8) * 2
+    w = 1 + _rand((H,), 9) * 0.1
+    b = _rand((H,), 10) * 0.1
+    dy = _rand(shape, 11)
+    _, mu, rstd = ext().layernorm_fwd(x, w, b, 1e-5)
+    dx, dw, db = ext().layernorm_bwd(dy, x, w, mu, rstd)
+
+    xr = x.float().requires_grad_(True)
+    wr = w.float().requires_grad_(True)
+    br = b.float().requires_grad_(True)
+    torch.nn.functional.layer_norm(xr, (H,), wr, br, 1e-5).backward(
+        dy.float())
+    for c0 in range(0, H, 2048):
+        sl = slice(c0, min(c0 + 2048, H))
+        errs = dict(dx=_rel_err(dx[..., sl], xr.grad[..., sl]),
+                    dw=_rel_err(dw[sl], wr.grad[sl]),
+                    db=_rel_err(db[sl], br.grad[sl]))
+        print(shape, "columns", sl.start, sl.stop, errs)
+        for k, e in errs.items():
+            assert e < 3e-2, (k, sl, errs)
+
+    dx2, dw2, db2 = ext().layernorm_bwd(dy, x, w, mu, rstd)
+    assert torch.equal(dx, dx2)
+    assert torch.equal(dw, dw2)
+    assert torch.equal(db, db2)
