@@ -501,6 +501,58 @@ void grad_scale_(torch::Tensor descs, int64_t nchunks, torch::Tensor sq_total,
                     cur_stream());
 }
 
+// ---------------- fp8 quantisation (fp8_quant.hip) ----------------
+// x: bf16 [R, C] on the GPU, contiguous, 16 B aligned, R and C multiples of
+// 16 (what the FP8 GEMM itself requires of every operand)
+inline void fp8_check_input(const torch::Tensor& x) {
+  CHECK_BF16_CONTIG(x);
+  TORCH_CHECK(x.dim() == 2, "fp8 quantisation expects a 2-D [R, C] tensor");
+  TORCH_CHECK(x.size(0) > 0 && x.size(1) > 0 && x.size(0) % 16 == 0 &&
+                  x.size(1) % 16 == 0,
+              "fp8 quantisation requires R and C to be positive multiples "
+              "of 16, got [", x.size(0), ", ", x.size(1), "]");
+  TORCH_CHECK(x.size(0) <= INT32_MAX && x.size(1) <= INT32_MAX,
+              "fp8 quantisation: R and C must fit in int32");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "fp8 quantisation requires a 16-byte aligned tensor");
+}
+
+// f32 [2] on x's device: {448 / max(amax, 1e-12), max(amax, 1e-12) / 448}
+torch::Tensor fp8_amax_scale(torch::Tensor x) {
+  fp8_check_input(x);
+  auto partials = torch::empty({(int64_t)fp8_amax_blocks(x.numel())},
+                               x.options().dtype(torch::kInt));
+  auto scales = torch::empty({2}, x.options().dtype(torch::kFloat));
+  fp8_amax_scale_launch(x.data_ptr(), x.numel(), partials.data_ptr(),
+                        scales.data_ptr<float>(), cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return scales;
+}
+
+// (q [R, C], qt [C, R]) in e4m3; an output not asked for comes back None
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+fp8_cast_transpose(torch::Tensor x, torch::Tensor scale, bool rowwise,
+                   bool transposed) {
+  fp8_check_input(x);
+  TORCH_CHECK(rowwise || transposed,
+              "fp8_cast_transpose: ask for at least one output");
+  TORCH_CHECK(scale.is_cuda() && scale.device() == x.device(),
+              "scale must be on x's device");
+  TORCH_CHECK(scale.dtype() == torch::kFloat && scale.numel() == 1,
+              "scale must be a single f32 value");
+  const int64_t R = x.size(0), C = x.size(1);
+  auto opts = x.options().dtype(at::kFloat8_e4m3fn);
+  c10::optional<torch::Tensor> q, qt;
+  if (rowwise) q = torch::empty({R, C}, opts);
+  if (transposed) qt = torch::empty({C, R}, opts);
+  fp8_cast_transpose_launch(x.data_ptr(), scale.data_ptr<float>(),
+                            q ? q->data_ptr() : nullptr,
+                            qt ? qt->data_ptr() : nullptr, (int)R, (int)C,
+                            cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {q, qt};
+}
+
 // ---------------- attention ----------------
 // doc_start / doc_end are the [B,S] int32 tables of ops/doc_mask.py (their
 // contents are the caller's contract; the kernels only keep a bad table
@@ -648,6 +700,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step_clipped", &adamw_step_clipped);
   m.def("grad_sqsum", &grad_sqsum);
   m.def("grad_scale_", &grad_scale_);
+  m.def("fp8_amax_scale", &fp8_amax_scale);
+  m.def("fp8_cast_transpose", &fp8_cast_transpose);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_fwd_doc", &attn_fwd_doc);

@@ -97,6 +97,19 @@ void grad_sqsum_launch(const void* descs, int nchunks, float* partials,
 void grad_scale_launch(const void* descs, int nchunks, const float* sq_total,
                        float max_norm, hipStream_t s);
 
+// fp8_quant.hip: tensor-wise e4m3 quantisation of a contiguous, 16 B aligned
+// bf16 [R, C] tensor, R % 16 == 0 and C % 16 == 0.  fp8_amax_scale_launch
+// writes scales[0] = 448 / max(amax, 1e-12) and scales[1] = its reciprocal
+// quotient; `partials` holds fp8_amax_blocks(numel) dwords and needs no
+// initialisation.  fp8_cast_transpose_launch writes the row-major e4m3
+// [R, C] to `q` and the transposed [C, R] to `qt`; a null pointer drops that
+// output (both null launches nothing).
+int fp8_amax_blocks(int64_t numel);
+void fp8_amax_scale_launch(const void* x, int64_t numel, void* partials,
+                           float* scales, hipStream_t s);
+void fp8_cast_transpose_launch(const void* x, const float* scale, void* q,
+                               void* qt, int R, int C, hipStream_t s);
+
 // attention_fwd.hip, attention_bwd.hip.  doc_start / doc_end are the [B,S]
 // int32 tables of the document-masked mode for packed rows (first token /
 // exclusive end of each token's document); null selects the plain causal

@@ -403,6 +403,8 @@ void norm_bwd_launch(const void* dy, const void* dres, const void* x,
 #undef NORM_BWD
   }
   colsum_launch(dw_partial, dw, nblocks, H, s);
-  if (ln) colsum_launch(db_partial, db, nblocks, H, s);
+  // keyed on db, not on ln: with zero rows LayerNorm's empty `mu` is a null
+  // pointer too, and db must still come out as zeros
+  if (db) colsum_launch(db_partial, db, nblocks, H, s);
 }
 }

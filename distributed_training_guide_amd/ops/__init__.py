@@ -4,6 +4,8 @@ from .attention import flash_attention
 from .cross_entropy import causal_lm_loss, sharded_causal_lm_loss
 from .doc_mask import (DocBounds, doc_bounds, doc_start_from_ids,
                        validate_doc_start)
+from .fp8_linear import (Fp8Linear, convert_linears_to_fp8, fp8_linear,
+                         fp8_quantize)
 from .fused_linear_ce import fused_causal_lm_loss
 from .grad_clip import clip_grad_norm_, grad_sq_sum
 from .layernorm import LayerNorm, gelu
@@ -20,6 +22,10 @@ __all__ = [
     "doc_bounds",
     "doc_start_from_ids",
     "validate_doc_start",
+    "Fp8Linear",
+    "convert_linears_to_fp8",
+    "fp8_linear",
+    "fp8_quantize",
     "fused_causal_lm_loss",
     "clip_grad_norm_",
     "grad_sq_sum",

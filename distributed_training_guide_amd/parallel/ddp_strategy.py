@@ -14,6 +14,8 @@ from .zero1 import ZeroRedundancyOptimizer
 
 
 class DDPStrategy:
+    supports_fp8 = True  # parameters stay whole on every rank
+
     def __init__(self, args):
         self.local_rank = env_local_rank()
         self.device = pick_device(args, self.local_rank)

@@ -12,6 +12,8 @@ from ..utils import checkpoint as ckpt
 
 
 class SingleDeviceStrategy:
+    supports_fp8 = True  # parameters stay whole on every rank
+
     def __init__(self, args):
         self.rank = 0
         self.local_rank = 0

@@ -11,7 +11,8 @@ skipping (01:86-106,133-135,181-187), epoch/sampler semantics (02:137).
 Extras the reference ships as diff-recipes are first-class flags:
 --grad-accum-steps (related-topics/gradient-accumulation, incl. no_sync),
 --deterministic + RNG checkpointing (related-topics/determinism),
---wandb (wandb-configurations topologies).
+--wandb (wandb-configurations topologies),
+--fp8 (FP8 projection GEMMs, ops/fp8_linear.py; Llama, single and DDP).
 """
 import argparse
 import logging
@@ -63,6 +64,10 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
                        help="synthetic dataset: write an EOS id at random "
                             "gaps of this mean length (0 = one document "
                             "per row)")
+        p.add_argument("--fp8", action="store_true",
+                       help="run the qkv/o/gate_up/down projection GEMMs in "
+                            "FP8 (e4m3, tensor-wise dynamic scaling); Llama "
+                            "models, single-device and DDP strategies only")
         p.add_argument("--deterministic", action="store_true")
         p.add_argument("--wandb", action="store_true")
         p.add_argument("--wandb-mode", default="rank0",
@@ -85,6 +90,37 @@ def pick_device(args, local_rank: int) -> torch.device:
     return torch.device("cpu")
 
 
+def check_fp8_supported(config, strategy):
+    """--fp8 start-up check: raise ValueError naming what is unsupported.
+    `strategy` is a Strategy instance or class; the ones whose parameters
+    stay whole on every rank declare `supports_fp8 = True`."""
+    name = getattr(strategy, "__name__", type(strategy).__name__)
+    if not getattr(strategy, "supports_fp8", False):
+        raise ValueError(
+            f"--fp8 is not supported with {name}: FP8 linears are "
+            "implemented for the single-device and DDP strategies only "
+            "(FSDP, TP and 2D shard the weights the cast kernels read)")
+    if getattr(config, "model_type", None) != "llama":
+        raise ValueError(
+            f"--fp8 is not supported for model type "
+            f"{getattr(config, 'model_type', None)!r}: only Llama models, "
+            "whose projections are bias-free, are converted (GPT-2's "
+            "linears carry biases)")
+
+
+def apply_fp8(model):
+    """Convert the Llama projections (qkv_proj, o_proj, gate_up_proj,
+    down_proj) to FP8 linears in place; lm_head and embeddings stay bf16."""
+    from .ops import convert_linears_to_fp8
+
+    names = convert_linears_to_fp8(model, skip=("lm_head",))
+    if not names:
+        raise ValueError("--fp8: the model has no bias-free linear with "
+                         "dimensions that are multiples of 16 to convert")
+    LOGGER.info(f"FP8 (e4m3) GEMMs in {len(names)} linears")
+    return names
+
+
 class TrainerState(dict):
     @classmethod
     def fresh(cls):
@@ -104,7 +140,11 @@ def run_training(args, strategy):
         torch.use_deterministic_algorithms(True)
 
     config = get_config(args.model_name)
+    if getattr(args, "fp8", False):
+        check_fp8_supported(config, strategy)
     model, optimizer, lr_scheduler = strategy.build(config, args)
+    if getattr(args, "fp8", False):
+        apply_fp8(model)
     n_local = sum(p.numel() for p in model.parameters())
     # under sharding the local tensor count is NOT the model size; the
     # config knows the true total (reference logs the full count, 01:52)
