@@ -64,6 +64,8 @@ def main(argv=None):
     config_json["train_micro_batch_size_per_gpu"] = args.batch_size
     config_json["gradient_accumulation_steps"] = max(
         1, getattr(args, "grad_accum_steps", 1))
+    if getattr(args, "master_weights", False):
+        config_json["master_weights"] = True  # the flag or the config key
 
     model_config = get_config(args.model_name)
     engine, _, _, lr_scheduler = engine_mod.initialize(

@@ -475,6 +475,32 @@ void adamw_step_clipped(torch::Tensor descs, int64_t nchunks, double lr,
                        (float)max_norm, cur_stream());
 }
 
+// master-weight form (adamw.hip MASTER instantiations): lo_ptrs is the
+// [nchunks] int64 table of companion pointers, sq_total absent = unclipped
+void adamw_master_step(torch::Tensor descs, torch::Tensor lo_ptrs,
+                       int64_t nchunks, double lr, double beta1, double beta2,
+                       double eps, double wd, int64_t step,
+                       c10::optional<torch::Tensor> sq_total,
+                       double max_norm) {
+  CHECK_DESCS(descs, nchunks);
+  TORCH_CHECK(lo_ptrs.is_cuda() && lo_ptrs.dtype() == torch::kLong &&
+              lo_ptrs.is_contiguous() && lo_ptrs.numel() >= nchunks &&
+              lo_ptrs.device() == descs.device(),
+              "lo_ptrs must be a cuda int64 table of >= nchunks pointers on "
+              "the descriptors' device");
+  const float* sq = nullptr;
+  if (sq_total.has_value()) {
+    CHECK_SQ_TOTAL(*sq_total, descs);
+    sq = sq_total->data_ptr<float>();
+  }
+  const float bc1 = 1.0f - std::pow((float)beta1, (float)step);
+  const float bc2 = 1.0f - std::pow((float)beta2, (float)step);
+  adamw_master_launch(descs.data_ptr(), lo_ptrs.data_ptr<int64_t>(),
+                      (int)nchunks, (float)lr, (float)beta1, (float)beta2,
+                      (float)eps, (float)wd, 1.0f / bc1, 1.0f / bc2, sq,
+                      (float)max_norm, cur_stream());
+}
+
 // ---------------- global grad norm / clipping ----------------
 void grad_sqsum(torch::Tensor descs, int64_t nchunks, torch::Tensor partials,
                 torch::Tensor out, int64_t slot) {
@@ -698,6 +724,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sharded"), py::arg("scale_t") = c10::nullopt);
   m.def("adamw_step", &adamw_step);
   m.def("adamw_step_clipped", &adamw_step_clipped);
+  m.def("adamw_master_step", &adamw_master_step);
   m.def("grad_sqsum", &grad_sqsum);
   m.def("grad_scale_", &grad_scale_);
   m.def("fp8_amax_scale", &fp8_amax_scale);

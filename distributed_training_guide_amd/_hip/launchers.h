@@ -92,6 +92,14 @@ void adamw_launch_clipped(const void* descs, int nchunks, float lr,
                           float beta1, float beta2, float eps, float wd,
                           float inv_bc1, float inv_bc2, const float* sq_total,
                           float max_norm, hipStream_t s);
+// Master-weight form: lo_tab is an [nchunks] table of device pointers to the
+// int16 companions of the bf16 chunks (0 for an fp32 chunk, which has none).
+// A null sq_total selects the unclipped instantiation.
+void adamw_master_launch(const void* descs, const int64_t* lo_tab,
+                         int nchunks, float lr, float beta1, float beta2,
+                         float eps, float wd, float inv_bc1, float inv_bc2,
+                         const float* sq_total, float max_norm,
+                         hipStream_t s);
 void grad_sqsum_launch(const void* descs, int nchunks, float* partials,
                        float* out, int slot, hipStream_t s);
 void grad_scale_launch(const void* descs, int nchunks, const float* sq_total,

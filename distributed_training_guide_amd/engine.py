@@ -37,6 +37,9 @@ DEFAULT_CONFIG = {
     "gradient_accumulation_steps": 1,
     # global grad-norm clipping (deepspeed's key): 0.0 = off
     "gradient_clipping": 0.0,
+    # 16-bit-extended fp32 master of the bf16 shards (FusedAdamW
+    # master_weights; not a deepspeed key): +2 B per parameter
+    "master_weights": False,
     "bf16": {"enabled": True},
     "zero_optimization": {
         "stage": 3,
@@ -93,7 +96,8 @@ class Engine(torch.nn.Module):
             eps=opt.get("eps", 1e-8),
             weight_decay=opt.get("weight_decay", 0.0),
             max_grad_norm=config.get("gradient_clipping", 0.0),
-            grad_norm_parts=self.module.grad_norm_parts())
+            grad_norm_parts=self.module.grad_norm_parts(),
+            master_weights=bool(config.get("master_weights", False)))
         self.lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             self.optimizer,
             T_max=config["scheduler"]["params"].get("t_max", 1000),

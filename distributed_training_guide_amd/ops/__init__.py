@@ -1,5 +1,5 @@
 """HIP-kernel-backed ops (GPU) with eager fp32 references (CPU/tests)."""
-from .adamw import FusedAdamW
+from .adamw import FusedAdamW, join_master, split_master
 from .attention import flash_attention
 from .cross_entropy import causal_lm_loss, sharded_causal_lm_loss
 from .doc_mask import (DocBounds, doc_bounds, doc_start_from_ids,
@@ -15,6 +15,8 @@ from .swiglu import silu_mul
 
 __all__ = [
     "FusedAdamW",
+    "split_master",
+    "join_master",
     "flash_attention",
     "causal_lm_loss",
     "sharded_causal_lm_loss",

@@ -38,10 +38,12 @@ class DDPStrategy:
         if self.use_zero1 and self.world_size > 1:
             optimizer = ZeroRedundancyOptimizer(
                 model.parameters(), optimizer_class=FusedAdamW, lr=args.lr,
-                max_grad_norm=max_grad_norm)
+                max_grad_norm=max_grad_norm,
+                master_weights=getattr(args, "master_weights", False))
         else:
-            optimizer = FusedAdamW(model.parameters(), lr=args.lr,
-                                   max_grad_norm=max_grad_norm)
+            optimizer = FusedAdamW(
+                model.parameters(), lr=args.lr, max_grad_norm=max_grad_norm,
+                master_weights=getattr(args, "master_weights", False))
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler

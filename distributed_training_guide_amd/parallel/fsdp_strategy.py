@@ -64,7 +64,8 @@ class FSDPStrategy:
         optimizer = FusedAdamW(
             model.parameters(), lr=args.lr,
             max_grad_norm=getattr(args, "max_grad_norm", 0.0),
-            grad_norm_parts=model.grad_norm_parts())
+            grad_norm_parts=model.grad_norm_parts(),
+            master_weights=getattr(args, "master_weights", False))
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler
@@ -121,11 +122,13 @@ def _load_resharding(exp_dir: Path, model, optimizer, rank):
     new_sd = {"state": {}, "param_groups": opt_sds[0]["param_groups"]}
     for i, u in enumerate(model.units):
         merged = {}
-        for key in ("exp_avg", "exp_avg_sq"):
+        for key in ("exp_avg", "exp_avg_sq", "master_lo"):
             if i in opt_sds[0]["state"] or str(i) in opt_sds[0]["state"]:
                 def get(sd):
                     st = sd["state"]
                     return st[i] if i in st else st[str(i)]
+                if not all(key in get(sd) for sd in opt_sds):
+                    continue  # master_lo: saved without --master-weights
                 full = torch.cat([get(sd)[key] for sd in opt_sds])
                 total = u.total
                 full = full[:total]

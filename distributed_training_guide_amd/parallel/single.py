@@ -29,7 +29,8 @@ class SingleDeviceStrategy:
         model = build_model(config, device=self.device, dtype=self.dtype)
         optimizer = FusedAdamW(
             model.parameters(), lr=args.lr,
-            max_grad_norm=getattr(args, "max_grad_norm", 0.0))
+            max_grad_norm=getattr(args, "max_grad_norm", 0.0),
+            master_weights=getattr(args, "master_weights", False))
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler

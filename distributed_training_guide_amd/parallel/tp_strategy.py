@@ -49,7 +49,8 @@ class TPStrategy:
         optimizer = FusedAdamW(
             model.parameters(), lr=args.lr,
             max_grad_norm=getattr(args, "max_grad_norm", 0.0),
-            grad_norm_parts=norm_parts)
+            grad_norm_parts=norm_parts,
+            master_weights=getattr(args, "master_weights", False))
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler
@@ -115,7 +116,10 @@ def _load_tp_resharding(exp_dir: Path, inner, optimizer):
         if get(opt_sds[0], i) is None:
             continue
         merged = {}
-        for key in ("exp_avg", "exp_avg_sq"):
+        keys = ["exp_avg", "exp_avg_sq"]
+        if all("master_lo" in get(sd, i) for sd in opt_sds):
+            keys.append("master_lo")  # follows its parameter's layout too
+        for key in keys:
             full = inner.reconstruct_full_tensor(
                 name, [get(sd, i)[key] for sd in opt_sds])
             merged[key] = inner.shard_tensor(name, full)
@@ -159,7 +163,9 @@ class TwoDStrategy(TPStrategy):
                      process_group=self.mesh.dp_group, device=self.device,
                      reduce_dtype=torch.float32,
                      cpu_offload=getattr(args, "cpu_offload", False))
-        optimizer = FusedAdamW(model.parameters(), lr=args.lr)
+        optimizer = FusedAdamW(
+            model.parameters(), lr=args.lr,
+            master_weights=getattr(args, "master_weights", False))
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(
             optimizer, T_max=1000, eta_min=args.lr * 1e-2)
         return model, optimizer, lr_scheduler

@@ -48,6 +48,9 @@ class ZeroRedundancyOptimizer(torch.optim.Optimizer):
             # only the moments are partitioned: every rank holds every
             # grad, so the clip norm runs over ALL params, not the partition
             kwargs.setdefault("grad_norm_parts", [(params, None)])
+        # master_weights= passes through like every keyword: local_opt owns
+        # the companions of its partition, and the bf16 values the
+        # all-gather below ships are the ones its own update wrote
         self.local_opt = optimizer_class(self.partitions[self.rank], **kwargs)
         # delegate Optimizer surface to the local optimizer (schedulers
         # mutate param_groups[...]["lr"] in place)

@@ -56,6 +56,12 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
         p.add_argument("--max-grad-norm", default=0.0, type=float,
                        help="clip the global gradient norm to this value, "
                             "fused into the AdamW update (0 = off)")
+        p.add_argument("--master-weights", action="store_true",
+                       help="keep an fp32 master of every bf16 parameter as "
+                            "the parameter plus an int16 remainder in the "
+                            "optimizer state (+2 B per parameter); without "
+                            "it an update below half a bf16 ulp is lost. "
+                            "No effect on parameters that are fp32 already")
         p.add_argument("--doc-mask", action="store_true",
                        help="confine attention to each token's own document "
                             "of a packed row (rows carry doc_start; Llama "
@@ -121,6 +127,18 @@ def apply_fp8(model):
     return names
 
 
+def log_master_weights(optimizer):
+    """--master-weights start-up line: how many parameters carry an int16
+    companion and what it costs on this rank."""
+    opt = getattr(optimizer, "local_opt", optimizer)  # ZeRO-1 wrapper
+    tensors, numel, nbytes = opt.master_summary()
+    LOGGER.info(f"Master weights: {tensors} bf16 parameter tensors "
+                f"({numel} elements) carry an int16 companion, "
+                f"+{nbytes / 2 ** 30:.3f} GiB of optimizer state on this "
+                "rank" + ("" if tensors else " (every parameter is fp32 "
+                          "already: the flag has no effect)"))
+
+
 class TrainerState(dict):
     @classmethod
     def fresh(cls):
@@ -145,6 +163,8 @@ def run_training(args, strategy):
     model, optimizer, lr_scheduler = strategy.build(config, args)
     if getattr(args, "fp8", False):
         apply_fp8(model)
+    if getattr(args, "master_weights", False):
+        log_master_weights(optimizer)
     n_local = sum(p.numel() for p in model.parameters())
     # under sharding the local tensor count is NOT the model size; the
     # config knows the true total (reference logs the full count, 01:52)
