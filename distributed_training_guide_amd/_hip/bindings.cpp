@@ -289,6 +289,104 @@ torch::Tensor qkv_rope_bwd(torch::Tensor dq, torch::Tensor dk,
   return dqkv;
 }
 
+// ---------------- fused qkv split + QK RMSNorm + rope ----------------
+struct QkvNormDims {
+  int64_t B, S, Hq, Hkv, D;
+};
+
+// what both entry points require of the packed qkv, the two norm weights and
+// the tables; `positions` is checked by rope_positions
+QkvNormDims qkv_norm_check(const torch::Tensor& qkv, const torch::Tensor& wq,
+                           const torch::Tensor& wk, const torch::Tensor& cos,
+                           const torch::Tensor& sin, int64_t Hq, int64_t Hkv,
+                           int64_t D) {
+  CHECK_BF16_CONTIG(qkv);
+  CHECK_BF16_CONTIG(wq);
+  CHECK_BF16_CONTIG(wk);
+  TORCH_CHECK(qkv.dim() == 3, "qkv_norm_rope expects qkv [B,S,W]");
+  TORCH_CHECK(D == 64 || D == 128,
+              "qkv_norm_rope: head dim must be 64 or 128, got ", D);
+  TORCH_CHECK(Hq > 0 && Hkv > 0, "qkv_norm_rope: head counts must be positive");
+  TORCH_CHECK(qkv.size(2) == (Hq + 2 * Hkv) * D,
+              "qkv_norm_rope: packed width mismatch, W must be (Hq+2*Hkv)*D");
+  TORCH_CHECK(wq.dim() == 1 && wq.size(0) == D && wk.dim() == 1 &&
+                  wk.size(0) == D,
+              "qkv_norm_rope: wq and wk must be [D]");
+  TORCH_CHECK(wq.device() == qkv.device() && wk.device() == qkv.device(),
+              "qkv_norm_rope: wq and wk must be on qkv's device");
+  TORCH_CHECK(qkv.size(0) <= 65535 && qkv.size(1) <= INT32_MAX,
+              "qkv_norm_rope: B must fit a grid dimension and S an int32");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(wk.data_ptr()) % 16 == 0,
+              "qkv_norm_rope: qkv, wq and wk must be 16-byte aligned");
+  CHECK_ROPE_TABLES(cos, sin, qkv, D);
+  return {qkv.size(0), qkv.size(1), Hq, Hkv, D};
+}
+
+std::vector<torch::Tensor> qkv_norm_rope_fwd(
+    torch::Tensor qkv, torch::Tensor wq, torch::Tensor wk, torch::Tensor cos,
+    torch::Tensor sin, c10::optional<torch::Tensor> positions, int64_t Hq,
+    int64_t Hkv, int64_t D, double eps) {
+  const QkvNormDims d = qkv_norm_check(qkv, wq, wk, cos, sin, Hq, Hkv, D);
+  const int* pos_ptr = rope_positions(positions, cos, qkv, d.S);
+  auto q = torch::empty({d.B, d.S, Hq, D}, qkv.options());
+  auto k = torch::empty({d.B, d.S, Hkv, D}, qkv.options());
+  auto v = torch::empty({d.B, d.S, Hkv, D}, qkv.options());
+  qkv_norm_rope_fwd_launch(qkv.data_ptr(), wq.data_ptr(), wk.data_ptr(),
+                           q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                           cos.data_ptr<float>(), sin.data_ptr<float>(),
+                           pos_ptr, d.B, (int)d.S, (int)Hq, (int)Hkv, (int)D,
+                           (float)eps, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {q, k, v};
+}
+
+// (dqkv [B,S,W], dwq [D], dwk [D]); dwq and dwk are the two halves of one
+// [2*D] tensor
+std::vector<torch::Tensor> qkv_norm_rope_bwd(
+    torch::Tensor dq, torch::Tensor dk, torch::Tensor dv, torch::Tensor qkv,
+    torch::Tensor wq, torch::Tensor wk, torch::Tensor cos, torch::Tensor sin,
+    c10::optional<torch::Tensor> positions, double eps) {
+  CHECK_BF16_CONTIG(dq);
+  CHECK_BF16_CONTIG(dk);
+  CHECK_BF16_CONTIG(dv);
+  TORCH_CHECK(dq.dim() == 4, "dq must be [B,S,Hq,D]");
+  TORCH_CHECK(dk.dim() == 4 && dk.size(0) == dq.size(0) &&
+                  dk.size(1) == dq.size(1) && dk.size(3) == dq.size(3),
+              "dk must be [B,S,Hkv,D]");
+  TORCH_CHECK(dv.sizes() == dk.sizes(), "dv must be [B,S,Hkv,D]");
+  TORCH_CHECK(dk.device() == dq.device() && dv.device() == dq.device() &&
+                  qkv.device() == dq.device(),
+              "dk, dv and qkv must be on dq's device");
+  const int64_t Hq = dq.size(2), Hkv = dk.size(2), D = dq.size(3);
+  const QkvNormDims d = qkv_norm_check(qkv, wq, wk, cos, sin, Hq, Hkv, D);
+  TORCH_CHECK(d.B == dq.size(0) && d.S == dq.size(1),
+              "qkv must be [B,S,W] with dq's B and S");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dq.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(dk.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(dv.data_ptr()) % 16 == 0,
+              "qkv_norm_rope: dq, dk and dv must be 16-byte aligned");
+  const int* pos_ptr = rope_positions(positions, cos, qkv, d.S);
+  auto dqkv = torch::empty_like(qkv);
+  if (d.B == 0 || d.S == 0) {
+    auto dw0 = torch::zeros({2 * D}, wq.options());
+    return {dqkv, dw0.narrow(0, 0, D), dw0.narrow(0, D, D)};
+  }
+  auto dw = torch::empty({2 * D}, wq.options());
+  const int nblocks = qkv_norm_rope_bwd_blocks(d.B, (int)d.S);
+  auto dw_partial = alloc_partials(nblocks, (int)(2 * D), qkv);
+  qkv_norm_rope_bwd_launch(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                           qkv.data_ptr(), wq.data_ptr(), wk.data_ptr(),
+                           dqkv.data_ptr(), dw_partial.data_ptr<float>(),
+                           dw.data_ptr(), cos.data_ptr<float>(),
+                           sin.data_ptr<float>(), pos_ptr, d.B, (int)d.S,
+                           (int)Hq, (int)Hkv, (int)D, (float)eps,
+                           cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {dqkv, dw.narrow(0, 0, D), dw.narrow(0, D, D)};
+}
+
 // ---------------- silu_mul ----------------
 torch::Tensor silu_mul_fwd(torch::Tensor gu) {
   CHECK_BF16_CONTIG(gu);
@@ -708,6 +806,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_rmsnorm_bwd", &add_rmsnorm_bwd);
   m.def("qkv_rope_fwd", &qkv_rope_fwd);
   m.def("qkv_rope_bwd", &qkv_rope_bwd);
+  m.def("qkv_norm_rope_fwd", &qkv_norm_rope_fwd);
+  m.def("qkv_norm_rope_bwd", &qkv_norm_rope_bwd);
   m.def("silu_mul_fwd", &silu_mul_fwd);
   m.def("silu_mul_bwd", &silu_mul_bwd);
   m.def("embedding_fwd", &embedding_fwd);

@@ -56,6 +56,25 @@ void qkv_rope_bwd_launch(const void* dq, const void* dk, const void* dv,
                          const int* positions, int64_t BS, int S, int Hq,
                          int Hkv, int D, hipStream_t stream);
 
+// qkv_norm_rope.hip: the qkv split with a per-head RMSNorm (weights wq / wk,
+// bf16 [D]) on every q and k row before the rotation; D is 64 or 128 and
+// qkv is [B,S,W].  The backward reads the saved qkv, writes
+// qkv_norm_rope_bwd_blocks(B, S) rows of `dw_partial` ([blocks + COLSUM_RY,
+// 2*D] f32, no initialisation needed) and finishes them with colsum_launch
+// into `dw` (bf16 [2*D]: dwq | dwk).  With B or S zero nothing is launched.
+int qkv_norm_rope_bwd_blocks(int64_t B, int S);
+void qkv_norm_rope_fwd_launch(const void* qkv, const void* wq, const void* wk,
+                              void* q, void* k, void* v, const float* cs,
+                              const float* sn, const int* positions,
+                              int64_t B, int S, int Hq, int Hkv, int D,
+                              float eps, hipStream_t stream);
+void qkv_norm_rope_bwd_launch(const void* dq, const void* dk, const void* dv,
+                              const void* qkv, const void* wq, const void* wk,
+                              void* dqkv, float* dw_partial, void* dw,
+                              const float* cs, const float* sn,
+                              const int* positions, int64_t B, int S, int Hq,
+                              int Hkv, int D, float eps, hipStream_t stream);
+
 // silu_mul.hip
 void silu_mul_fwd_launch(const void* gu, void* y, int64_t nrows, int I,
                          hipStream_t s);

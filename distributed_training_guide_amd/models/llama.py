@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import (RMSNorm, causal_lm_loss, doc_bounds, flash_attention,
-                   qkv_rope, silu_mul)
+                   qkv_norm_rope, qkv_rope, silu_mul)
 from ..ops.embedding import Embedding
 from ..ops.fused_linear_ce import fused_causal_lm_loss
 from ..ops.rmsnorm import add_rmsnorm
@@ -45,9 +45,17 @@ class LlamaConfig:
     initializer_range: float = 0.02
     tie_word_embeddings: bool = False
     model_type: str = field(default="llama")
+    # QK-norm (Qwen3, OLMo-2, Gemma-3): an RMSNorm with a learned [head_dim]
+    # weight on every q and k head, after the projection and before RoPE
+    qk_norm: bool = False
+    # explicit head dim for models that decouple it from hidden / heads
+    # (Qwen3 uses 128 throughout); None = hidden_size // num_attention_heads
+    head_dim_override: int | None = None
 
     @property
     def head_dim(self) -> int:
+        if self.head_dim_override is not None:
+            return self.head_dim_override
         return self.hidden_size // self.num_attention_heads
 
     @property
@@ -57,7 +65,11 @@ class LlamaConfig:
     def num_parameters(self) -> int:
         h, i, v = self.hidden_size, self.intermediate_size, self.padded_vocab_size
         d = self.head_dim
-        attn = h * (self.num_attention_heads + 2 * self.num_key_value_heads) * d + h * h
+        hq = self.num_attention_heads
+        # o_proj is [h, Hq*d]: h*h unless the head dim is set explicitly
+        attn = h * (hq + 2 * self.num_key_value_heads) * d + hq * d * h
+        if self.qk_norm:
+            attn += 2 * d
         mlp = 3 * h * i
         per_layer = attn + mlp + 2 * h
         embed = v * h * (1 if self.tie_word_embeddings else 2)
@@ -85,16 +97,29 @@ class LlamaAttention(nn.Module):
             device=device, dtype=dtype)
         self.o_proj = nn.Linear(self.num_heads * d, h, bias=False,
                                 device=device, dtype=dtype)
+        if config.qk_norm:
+            # weight holders (HF names self_attn.q_norm / k_norm): forward
+            # hands their weights to the fused split + norm + RoPE kernel
+            self.q_norm = RMSNorm(d, config.rms_norm_eps, device, dtype)
+            self.k_norm = RMSNorm(d, config.rms_norm_eps, device, dtype)
 
     def forward(self, x, position_ids=None, doc=None):
         B, S, _ = x.shape
         d = self.head_dim
         qkv = self.qkv_proj(x)
-        # fused split + RoPE: one pass, no intermediate copies, backward
-        # writes dqkv directly (no grad cat)
-        q, k, v = qkv_rope(qkv, self.num_heads, self.num_kv_heads, d,
-                           self.config.rope_theta, positions=position_ids,
-                           max_pos=self.config.max_position_embeddings)
+        if self.config.qk_norm:
+            # fused split + per-head RMSNorm of q and k + RoPE
+            q, k, v = qkv_norm_rope(
+                qkv, self.q_norm.weight, self.k_norm.weight, self.num_heads,
+                self.num_kv_heads, d, self.q_norm.eps,
+                self.config.rope_theta, positions=position_ids,
+                max_pos=self.config.max_position_embeddings)
+        else:
+            # fused split + RoPE: one pass, no intermediate copies, backward
+            # writes dqkv directly (no grad cat)
+            q, k, v = qkv_rope(qkv, self.num_heads, self.num_kv_heads, d,
+                               self.config.rope_theta, positions=position_ids,
+                               max_pos=self.config.max_position_embeddings)
         o = flash_attention(q, k, v, doc=doc)
         return self.o_proj(o.reshape(B, S, self.num_heads * d))
 
@@ -175,7 +200,8 @@ class LlamaForCausalLM(nn.Module):
         (reference flow 04:74-95)."""
         std = self.config.initializer_range
         with torch.no_grad():
-            if "layernorm" in name or name.startswith("norm."):
+            if "layernorm" in name or name.startswith("norm.") \
+                    or ".q_norm." in name or ".k_norm." in name:
                 tensor.fill_(1.0)
             elif name.endswith(".bias"):
                 tensor.zero_()

@@ -20,6 +20,26 @@ _LLAMA_CONFIGS = {
     "llama-60m": (512, 1376, 8, 8, 8, 32000, 1e4, 2048),
 }
 
+# Qwen3 dense models: QK-norm, head_dim 128 whatever hidden / heads is,
+# vocab 151936, rope_theta 1e6, rms_norm_eps 1e-6, 40960 positions (vocab,
+# head_dim and eps are also transformers' Qwen3Config defaults; the
+# per-size rows are the published model cards' values)
+_QWEN3_CONFIGS = {
+    # name -> (hidden, intermediate, layers, heads, kv_heads, tied embeddings)
+    "qwen3-0.6b": (1024, 3072, 28, 16, 8, True),
+    "qwen3-1.7b": (2048, 6144, 28, 16, 8, True),
+    "qwen3-4b": (2560, 9728, 36, 32, 8, True),
+    "qwen3-8b": (4096, 12288, 36, 32, 8, False),
+    "qwen3-14b": (5120, 17408, 40, 40, 8, False),
+    "qwen3-32b": (5120, 25600, 64, 64, 8, False),
+}
+_QWEN3_COMMON = dict(vocab_size=151936, rope_theta=1e6, rms_norm_eps=1e-6,
+                     max_position_embeddings=40960)
+# small config for tests: Hq * head_dim = 512 != hidden
+_QWEN3_DEBUG = dict(vocab_size=1024, rope_theta=1e6, rms_norm_eps=1e-6,
+                    max_position_embeddings=2048)
+_QWEN3_CONFIGS["qwen3-debug"] = (256, 688, 4, 4, 2, False)
+
 _GPT2_CONFIGS = {
     # name -> (hidden, layers, heads); head_dim is 64 throughout
     "gpt2": (768, 12, 12),
@@ -46,6 +66,10 @@ _ALIASES = {
     "meta-llama/llama-3.2-1b": "llama-3.2-1b",
     "meta-llama/llama-3.2-3b": "llama-3.2-3b",
 }
+for _name in _QWEN3_CONFIGS:
+    if _name != "qwen3-debug":
+        _ALIASES[f"qwen/{_name}"] = _name
+        _ALIASES[f"qwen/{_name}-base"] = _name
 
 
 def resolve_name(name: str) -> str:
@@ -68,9 +92,18 @@ def get_config(name: str):
             rope_theta=theta,
             tie_word_embeddings=key.startswith("llama-3.2"),
         )
+    if key in _QWEN3_CONFIGS:
+        h, i, L, hq, hkv, tied = _QWEN3_CONFIGS[key]
+        common = _QWEN3_DEBUG if key == "qwen3-debug" else _QWEN3_COMMON
+        return LlamaConfig(
+            hidden_size=h, intermediate_size=i, num_hidden_layers=L,
+            num_attention_heads=hq, num_key_value_heads=hkv,
+            tie_word_embeddings=tied, qk_norm=True, head_dim_override=128,
+            **common)
     raise ValueError(
         f"unknown model {name!r}; known: "
-        f"{', '.join(_GPT2_CONFIGS)}, {', '.join(_LLAMA_CONFIGS)}")
+        f"{', '.join(_GPT2_CONFIGS)}, {', '.join(_LLAMA_CONFIGS)}, "
+        f"{', '.join(_QWEN3_CONFIGS)}")
 
 
 def build_model(name_or_config, device=None, dtype=None):

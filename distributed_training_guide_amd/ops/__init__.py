@@ -9,6 +9,7 @@ from .fp8_linear import (Fp8Linear, convert_linears_to_fp8, fp8_linear,
 from .fused_linear_ce import fused_causal_lm_loss
 from .grad_clip import clip_grad_norm_, grad_sq_sum
 from .layernorm import LayerNorm, gelu
+from .qk_norm import qkv_norm_rope
 from .rmsnorm import RMSNorm, rmsnorm
 from .rope import qkv_rope, rope
 from .swiglu import silu_mul
@@ -35,6 +36,7 @@ __all__ = [
     "gelu",
     "RMSNorm",
     "rmsnorm",
+    "qkv_norm_rope",
     "qkv_rope",
     "rope",
     "silu_mul",

@@ -27,7 +27,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..models.llama import CausalLMOutput, LlamaConfig
-from ..ops import RMSNorm, doc_bounds, flash_attention, rope, silu_mul
+from ..ops import (RMSNorm, doc_bounds, flash_attention, qkv_norm_rope, rope,
+                   silu_mul)
 from ..ops.cross_entropy import causal_lm_loss, sharded_causal_lm_loss
 
 LOGGER = logging.getLogger(__name__)
@@ -257,11 +258,24 @@ class TPLlamaAttention(nn.Module):
             device=device, dtype=dtype)
         self.o_proj = RowwiseLinear(config.num_attention_heads * d, h, mesh,
                                     device=device, dtype=dtype)
+        if config.qk_norm:
+            # [head_dim] weights shared by all heads: replicated over tp
+            self.q_norm = RMSNorm(d, config.rms_norm_eps, device, dtype)
+            self.k_norm = RMSNorm(d, config.rms_norm_eps, device, dtype)
 
     def forward(self, x, position_ids=None, doc=None):
         B, S, _ = x.shape  # x is REPLICATED (post seq-gather), full S
         d = self.head_dim
         qkv = self.qkv_proj(x)
+        if self.config.qk_norm:
+            # the ColwiseLinear segments leave the local q|k|v packed
+            q, k, v = qkv_norm_rope(
+                qkv, self.q_norm.weight, self.k_norm.weight, self.num_heads,
+                self.num_kv_heads, d, self.q_norm.eps,
+                self.config.rope_theta, positions=position_ids,
+                max_pos=self.config.max_position_embeddings)
+            o = flash_attention(q, k, v, doc=doc)
+            return self.o_proj(o.reshape(B, S, self.num_heads * d))
         q, k, v = qkv.split([self.num_heads * d, self.num_kv_heads * d,
                              self.num_kv_heads * d], dim=-1)
         q = q.view(B, S, self.num_heads, d)
@@ -357,6 +371,9 @@ class TPLlamaForCausalLM(nn.Module):
                 layer.self_attn.qkv_proj.load_full_weight(
                     full(((hq + 2 * hkv) * d, h)), tr)
                 layer.self_attn.o_proj.load_full_weight(full((h, hq * d)), tr)
+                if cfg.qk_norm:
+                    layer.self_attn.q_norm.weight.fill_(1.0)
+                    layer.self_attn.k_norm.weight.fill_(1.0)
                 layer.mlp.gate_up_proj.load_full_weight(full((2 * i, h)), tr)
                 layer.mlp.down_proj.load_full_weight(full((h, i)), tr)
             self.norm.weight.fill_(1.0)
@@ -368,7 +385,10 @@ class TPLlamaForCausalLM(nn.Module):
 
     def _register_replicated_grad_hooks(self):
         """Norm weights are tp-replicated; each rank's grad covers only its
-        sequence shard -> sum over the tp group when the grad is ready."""
+        shard of the rows the norm saw -> sum over the tp group when the
+        grad is ready.  For the layer norms that is a sequence shard; for
+        the QK-norm weights (q_norm / k_norm, RMSNorm instances too) every
+        rank sees the full sequence but only its own heads: a head shard."""
         g = self.mesh.tp_group
         if self.mesh.tp_size == 1:
             return
