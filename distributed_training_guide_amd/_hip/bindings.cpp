@@ -387,6 +387,157 @@ std::vector<torch::Tensor> qkv_norm_rope_bwd(
   return {dqkv, dw.narrow(0, 0, D), dw.narrow(0, D, D)};
 }
 
+// ---------------- mixture of experts (moe_router.hip, moe_dispatch.hip) ----
+#define CHECK_ON_DEVICE_CONTIG(t, ref, type, what)                         \
+  TORCH_CHECK((t).is_cuda() && (t).device() == (ref).device(),             \
+              #t " must be on " #ref "'s device");                         \
+  TORCH_CHECK((t).dtype() == (type) && (t).is_contiguous(),                \
+              #t " must be contiguous " what)
+
+// logits bf16 [T, E] with a supported E, and k in range for it
+inline void moe_router_check(const torch::Tensor& logits, int64_t k) {
+  CHECK_BF16_CONTIG(logits);
+  TORCH_CHECK(logits.dim() == 2, "moe_router: logits must be [T, E]");
+  const int64_t E = logits.size(1);
+  TORCH_CHECK(E == 8 || E == 16 || E == 32 || E == 64 || E == 128,
+              "moe_router: E must be 8, 16, 32, 64 or 128, got ", E);
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= E,
+              "moe_router: k must be in [1, min(8, E)], got ", k);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 4 == 0,
+              "moe_router: logits must be 4-byte aligned");
+}
+
+std::vector<torch::Tensor> moe_router_fwd(torch::Tensor logits, int64_t k,
+                                          bool norm) {
+  moe_router_check(logits, k);
+  const int64_t T = logits.size(0), E = logits.size(1);
+  auto idx = torch::empty({T, k}, logits.options().dtype(torch::kInt));
+  auto w = torch::empty({T, k}, logits.options().dtype(torch::kFloat));
+  moe_router_fwd_launch(logits.data_ptr(), idx.data_ptr<int>(),
+                        w.data_ptr<float>(), T, (int)E, (int)k, norm ? 1 : 0,
+                        cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {idx, w};
+}
+
+torch::Tensor moe_router_bwd(torch::Tensor logits, torch::Tensor topk_idx,
+                             torch::Tensor d_topk_w, bool norm) {
+  TORCH_CHECK(topk_idx.dim() == 2, "topk_idx must be [T, k]");
+  const int64_t k = topk_idx.size(1);
+  moe_router_check(logits, k);
+  const int64_t T = logits.size(0), E = logits.size(1);
+  CHECK_ON_DEVICE_CONTIG(topk_idx, logits, torch::kInt, "int32");
+  CHECK_ON_DEVICE_CONTIG(d_topk_w, logits, torch::kFloat, "f32");
+  TORCH_CHECK(topk_idx.size(0) == T && d_topk_w.sizes() == topk_idx.sizes(),
+              "topk_idx and d_topk_w must be [T, k] with the logits' T");
+  auto dlogits = torch::empty_like(logits);
+  moe_router_bwd_launch(logits.data_ptr(), topk_idx.data_ptr<int>(),
+                        d_topk_w.data_ptr<float>(), dlogits.data_ptr(), T,
+                        (int)E, (int)k, norm ? 1 : 0, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dlogits;
+}
+
+// (dest [T*k], offs [E]): views of one int32 buffer whose tail is the index
+// build's scratch
+std::vector<torch::Tensor> moe_dispatch_index(torch::Tensor topk_idx,
+                                              int64_t E) {
+  TORCH_CHECK(topk_idx.is_cuda(), "topk_idx must be on the GPU");
+  TORCH_CHECK(topk_idx.dtype() == torch::kInt && topk_idx.is_contiguous(),
+              "topk_idx must be contiguous int32");
+  TORCH_CHECK(topk_idx.dim() == 2, "topk_idx must be [T, k]");
+  TORCH_CHECK(E == 8 || E == 16 || E == 32 || E == 64 || E == 128,
+              "moe_dispatch_index: E must be 8, 16, 32, 64 or 128, got ", E);
+  const int64_t N = topk_idx.numel();
+  TORCH_CHECK(N <= INT32_MAX, "moe_dispatch_index: T*k must fit an int32");
+  auto buf = torch::empty({N + E + moe_index_scratch(N, (int)E)},
+                          topk_idx.options());
+  int* p = buf.data_ptr<int>();
+  moe_index_launch(topk_idx.data_ptr<int>(), p, p + N, p + N + E, N, (int)E,
+                   cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {buf.narrow(0, 0, N), buf.narrow(0, N, E)};
+}
+
+// what the row movers require: rows bf16 [R, H] with H % 8 == 0, dest int32
+// [N] on the rows' device; moe_k_check then derives k = N / T
+inline void moe_rows_check(const torch::Tensor& rows, const torch::Tensor& dest,
+                           const char* what) {
+  CHECK_BF16_CONTIG(rows);
+  TORCH_CHECK(rows.dim() == 2, what, ": rows must be [R, H]");
+  TORCH_CHECK(rows.size(1) > 0 && rows.size(1) % 8 == 0 &&
+                  rows.size(1) <= INT32_MAX,
+              what, ": H must be a positive multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0, what,
+              ": rows must be 16-byte aligned");
+  CHECK_ON_DEVICE_CONTIG(dest, rows, torch::kInt, "int32");
+  TORCH_CHECK(dest.dim() == 1, what, ": dest must be [T*k]");
+}
+
+inline int64_t moe_k_check(int64_t T, int64_t N, const char* what) {
+  TORCH_CHECK(N == 0 ? T == 0 : (T > 0 && N % T == 0 && N / T <= 8), what,
+              ": dest must hold k <= 8 slots per token");
+  return T == 0 ? 1 : N / T;
+}
+
+// xp [T*k, H]: a copy of x[t] at every row dest[t*k + j]
+torch::Tensor moe_scatter(torch::Tensor x, torch::Tensor dest) {
+  moe_rows_check(x, dest, "moe_scatter");
+  const int64_t T = x.size(0), H = x.size(1), N = dest.numel();
+  const int64_t k = moe_k_check(T, N, "moe_scatter");
+  auto xp = torch::empty({N, H}, x.options());
+  moe_scatter_launch(x.data_ptr(), dest.data_ptr<int>(), nullptr, nullptr,
+                     xp.data_ptr(), nullptr, T, (int)H, (int)k, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return xp;
+}
+
+// y [T, H] = sum_j w[t, j] * yp[dest[t*k + j]]; without w the weights are 1
+torch::Tensor moe_combine(torch::Tensor yp, torch::Tensor dest,
+                          c10::optional<torch::Tensor> w, int64_t k) {
+  moe_rows_check(yp, dest, "moe_combine");
+  const int64_t N = dest.numel(), H = yp.size(1);
+  TORCH_CHECK(yp.size(0) == N, "moe_combine: yp must be [T*k, H]");
+  TORCH_CHECK(k >= 1 && k <= 8 && N % k == 0,
+              "moe_combine: k must be in [1, 8] and divide dest's length");
+  const int64_t T = N / k;
+  const float* wp = nullptr;
+  if (w.has_value()) {
+    CHECK_ON_DEVICE_CONTIG(*w, yp, torch::kFloat, "f32");
+    TORCH_CHECK(w->dim() == 2 && w->size(0) == T && w->size(1) == k,
+                "moe_combine: w must be [T, k]");
+    wp = w->data_ptr<float>();
+  }
+  auto y = torch::empty({T, H}, yp.options());
+  moe_combine_launch(yp.data_ptr(), dest.data_ptr<int>(), wp, y.data_ptr(), T,
+                     (int)H, (int)k, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return y;
+}
+
+// the combine's backward: (dyp [T*k, H], dw [T, k])
+std::vector<torch::Tensor> moe_combine_bwd(torch::Tensor dy,
+                                           torch::Tensor dest,
+                                           torch::Tensor w,
+                                           torch::Tensor yp) {
+  moe_rows_check(dy, dest, "moe_combine_bwd");
+  moe_rows_check(yp, dest, "moe_combine_bwd");
+  const int64_t T = dy.size(0), H = dy.size(1), N = dest.numel();
+  CHECK_ON_DEVICE_CONTIG(w, dy, torch::kFloat, "f32");
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == T && w.numel() == N,
+              "moe_combine_bwd: w must be [T, k]");
+  const int64_t k = moe_k_check(T, N, "moe_combine_bwd");
+  TORCH_CHECK(yp.size(0) == N && yp.size(1) == H,
+              "moe_combine_bwd: yp must be [T*k, H]");
+  auto dyp = torch::empty_like(yp);
+  auto dw = torch::empty_like(w);
+  moe_scatter_launch(dy.data_ptr(), dest.data_ptr<int>(), w.data_ptr<float>(),
+                     yp.data_ptr(), dyp.data_ptr(), dw.data_ptr<float>(), T,
+                     (int)H, (int)k, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {dyp, dw};
+}
+
 // ---------------- silu_mul ----------------
 torch::Tensor silu_mul_fwd(torch::Tensor gu) {
   CHECK_BF16_CONTIG(gu);
@@ -808,6 +959,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qkv_rope_bwd", &qkv_rope_bwd);
   m.def("qkv_norm_rope_fwd", &qkv_norm_rope_fwd);
   m.def("qkv_norm_rope_bwd", &qkv_norm_rope_bwd);
+  m.def("moe_router_fwd", &moe_router_fwd);
+  m.def("moe_router_bwd", &moe_router_bwd);
+  m.def("moe_dispatch_index", &moe_dispatch_index);
+  m.def("moe_scatter", &moe_scatter);
+  m.def("moe_combine", &moe_combine);
+  m.def("moe_combine_bwd", &moe_combine_bwd);
   m.def("silu_mul_fwd", &silu_mul_fwd);
   m.def("silu_mul_bwd", &silu_mul_bwd);
   m.def("embedding_fwd", &embedding_fwd);

@@ -81,6 +81,38 @@ void silu_mul_fwd_launch(const void* gu, void* y, int64_t nrows, int I,
 void silu_mul_bwd_launch(const void* dy, const void* gu, void* dgu,
                          int64_t nrows, int I, hipStream_t s);
 
+// moe_router.hip: top-k routing over bf16 logits [T, E], E in {8, 16, 32,
+// 64, 128} and 1 <= k <= min(8, E).  topk_idx is int32 [T, k], topk_w and
+// d_topk_w f32 [T, k]; `norm` selects the softmax over the k selected logits
+// (otherwise the full softmax's values at the selection).  The backward
+// writes every element of dlogits (bf16 [T, E]).  T == 0 launches nothing.
+void moe_router_fwd_launch(const void* logits, int* topk_idx, float* topk_w,
+                           int64_t T, int E, int k, int norm, hipStream_t s);
+void moe_router_bwd_launch(const void* logits, const int* topk_idx,
+                           const float* d_topk_w, void* dlogits, int64_t T,
+                           int E, int k, int norm, hipStream_t s);
+
+// moe_dispatch.hip.  moe_index_launch turns topk_idx (N = T*k slots, values
+// in [0, E)) into dest int32 [N] (the slot's row in the expert-sorted
+// layout) and offs int32 [E] (inclusive cumulative rows per expert); `hist`
+// is moe_index_scratch(N, E) int32 of scratch that needs no initialisation.
+// N == 0 is fine: offs comes out as zeros.
+// moe_scatter_launch: bf16 rows of H % 8 == 0 elements, 16 B aligned.  With
+// a null `w` it copies x[t] to xp[dest[t*k + j]] for every j and ignores
+// `yp` and `dw` (null); with `w` (f32 [T, k]) it writes
+// xp[dest[s]] = w[s] * x[t] and dw[s] = <x[t], yp[dest[s]]>.
+// moe_combine_launch: y[t] = sum_j w[t, j] * yp[dest[t*k + j]]; a null `w`
+// means weights of one.  dest must be a permutation of [0, N): the kernels
+// index rows with it unchecked.
+int64_t moe_index_scratch(int64_t N, int E);
+void moe_index_launch(const int* topk_idx, int* dest, int* offs, int* hist,
+                      int64_t N, int E, hipStream_t s);
+void moe_scatter_launch(const void* x, const int* dest, const float* w,
+                        const void* yp, void* xp, float* dw, int64_t T, int H,
+                        int k, hipStream_t s);
+void moe_combine_launch(const void* yp, const int* dest, const float* w,
+                        void* y, int64_t T, int H, int k, hipStream_t s);
+
 // embedding.hip
 void embed_fwd_launch(const void* table, const int64_t* ids, void* out,
                       int64_t nrows, int H, int64_t V, hipStream_t s);

@@ -1,0 +1,236 @@
+// Fused mixture-of-experts router for gfx950: softmax -> top-k ->
+// renormalise over the router GEMM's bf16 logits [T, E] in one pass, and its
+// backward in one pass (ops/moe.py).
+//
+// Forward outputs: topk_idx int32 [T, k] and topk_w f32 [T, k].  Selection
+// runs on the raw logits widened to f32 (exact), descending, a tie going to
+// the lower expert index: the first k of a stable descending sort.  With
+// NORM (Qwen3-MoE's norm_topk_prob) the weights are the softmax over the k
+// selected logits, otherwise the full softmax's values at the selection.
+// Either way w_j = exp(x_j - m) / Z with m the row maximum, which is the
+// first selected value, and Z summed over the selection (NORM) or the row.
+// Backward: with p_e = exp(x_e - m) / Z (zero outside the selection under
+// NORM) and g_e the incoming d_topk_w of a selected expert (zero otherwise),
+//   dlogits_e = p_e * (g_e - sum_e' p_e' g_e')
+// rounded once to bf16.  Nothing but the logits and topk_idx is kept from
+// the forward: p is recomputed.
+//
+// Mapping.  A token's E logits live in the lanes of one wave: LPT = min(E, 64)
+// lanes hold VPL = E / LPT values each (2 adjacent experts, one 4-byte load,
+// at E = 128), and 64 / LPT tokens share a wave.  LPT divides 64, so a
+// token's lane group never straddles a wavefront and every reduction is a
+// __shfl_xor butterfly over log2(LPT) steps.  Top-k is k rounds of a
+// butterfly arg-max over (value, index): every lane of the group ends the
+// round with the same winner, the lane that owns it retires it, and the
+// group's lane j keeps round j's winner for the store.  No LDS, no second
+// pass, no register array with a run-time index; token and expert come from
+// block, wave and lane with shifts and masks only.
+#include "common.h"
+#include "launchers.h"
+
+constexpr int MR_WAVES = 4;
+constexpr int MR_GRID_CAP = 2048;
+
+template <int LPT>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = LPT / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+  return v;
+}
+
+template <int LPT>
+__device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+  for (int off = LPT / 2; off > 0; off >>= 1)
+    v = fmaxf(v, __shfl_xor(v, off, WAVE));
+  return v;
+}
+
+// (v, i) beats (ov, oi) in a stable descending sort
+__device__ __forceinline__ bool mr_better(float v, int i, float ov, int oi) {
+  return v > ov || (v == ov && i < oi);
+}
+
+// The lane's VPL logits of token t (row-major [T, E]) widened to f32; x1 is
+// unused when VPL == 1.
+template <int E, int VPL>
+__device__ __forceinline__ void mr_load(const short* __restrict__ logits,
+                                        int64_t t, int e0, float& x0,
+                                        float& x1) {
+  if constexpr (VPL == 2) {
+    const uint32_t u =
+        *reinterpret_cast<const uint32_t*>(logits + t * E + e0);
+    x0 = bf2f((short)(u & 0xffffu));
+    x1 = bf2f((short)(u >> 16));
+  } else {
+    x0 = bf2f(logits[t * E + e0]);
+    x1 = -INFINITY;
+  }
+}
+
+template <int E, bool NORM>
+__global__ void __launch_bounds__(256) moe_router_fwd_kernel(
+    const short* __restrict__ logits, int* __restrict__ topk_idx,
+    float* __restrict__ topk_w, int64_t T, int k) {
+  constexpr int LPT = E < WAVE ? E : WAVE;
+  constexpr int VPL = E / LPT;
+  constexpr int TPW = WAVE / LPT;
+  constexpr int RETIRED = 2 * E;  // index of a retired value: loses every tie
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int sl = lane & (LPT - 1);  // lane within the token's group
+  const int e0 = sl * VPL;
+  const int64_t step = (int64_t)gridDim.x * MR_WAVES * TPW;
+  const int64_t first = ((int64_t)blockIdx.x * MR_WAVES + wid) * TPW;
+  // the bound is on the wave's first token: all lanes of a wave leave together
+  for (int64_t t0 = first; t0 < T; t0 += step) {
+    const int64_t t = t0 + (TPW > 1 ? lane / LPT : 0);
+    const bool live = t < T;
+    float x0 = 0.f, x1 = -INFINITY;
+    if (live) mr_load<E, VPL>(logits, t, e0, x0, x1);
+
+    bool took0 = false, took1 = (VPL == 1);
+    float m = 0.f, z = 0.f;  // row max (round 0's winner), sum of exp
+    float myv = 0.f;
+    int myi = 0;
+    for (int j = 0; j < k; ++j) {
+      // the lane's best value still in play; a retired slot stands as
+      // (-inf, RETIRED) and so loses to a live -inf logit as well
+      float bv = took0 ? -INFINITY : x0;
+      int bi = took0 ? RETIRED : e0;
+      if constexpr (VPL == 2) {
+        const float cv = took1 ? -INFINITY : x1;
+        const int ci = took1 ? RETIRED : e0 + 1;
+        if (mr_better(cv, ci, bv, bi)) {
+          bv = cv;
+          bi = ci;
+        }
+      }
+#pragma unroll
+      for (int off = LPT / 2; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off, WAVE);
+        const int oi = __shfl_xor(bi, off, WAVE);
+        if (mr_better(ov, oi, bv, bi)) {
+          bv = ov;
+          bi = oi;
+        }
+      }
+      took0 = took0 || bi == e0;
+      if constexpr (VPL == 2) took1 = took1 || bi == e0 + 1;
+      if (j == 0) m = bv;
+      if (NORM) z += expf(bv - m);
+      if (sl == j) {
+        myv = bv;
+        myi = bi;
+      }
+    }
+    if (!NORM) {
+      float zz = expf(x0 - m);
+      if constexpr (VPL == 2) zz += expf(x1 - m);
+      z = group_sum<LPT>(zz);
+    }
+    if (live && sl < k) {
+      topk_idx[t * k + sl] = myi;
+      topk_w[t * k + sl] = expf(myv - m) / z;
+    }
+  }
+}
+
+template <int E, bool NORM>
+__global__ void __launch_bounds__(256) moe_router_bwd_kernel(
+    const short* __restrict__ logits, const int* __restrict__ topk_idx,
+    const float* __restrict__ d_topk_w, short* __restrict__ dlogits,
+    int64_t T, int k) {
+  constexpr int LPT = E < WAVE ? E : WAVE;
+  constexpr int VPL = E / LPT;
+  constexpr int TPW = WAVE / LPT;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int sl = lane & (LPT - 1);
+  const int e0 = sl * VPL;
+  const int64_t step = (int64_t)gridDim.x * MR_WAVES * TPW;
+  const int64_t first = ((int64_t)blockIdx.x * MR_WAVES + wid) * TPW;
+  for (int64_t t0 = first; t0 < T; t0 += step) {
+    const int64_t t = t0 + (TPW > 1 ? lane / LPT : 0);
+    const bool live = t < T;
+    float x0 = 0.f, x1 = -INFINITY;
+    if (live) mr_load<E, VPL>(logits, t, e0, x0, x1);
+    // the selection and its incoming gradient: k broadcast loads per group
+    bool sel0 = false, sel1 = false;
+    float g0 = 0.f, g1 = 0.f;
+    if (live) {
+      for (int j = 0; j < k; ++j) {
+        const int e = topk_idx[t * k + j];
+        const float g = d_topk_w[t * k + j];
+        if (e == e0) {
+          sel0 = true;
+          g0 = g;
+        }
+        if (VPL == 2 && e == e0 + 1) {
+          sel1 = true;
+          g1 = g;
+        }
+      }
+    }
+    float mx = x0;
+    if constexpr (VPL == 2) mx = fmaxf(x0, x1);
+    const float m = group_max<LPT>(mx);
+    float p0 = (NORM && !sel0) ? 0.f : expf(x0 - m);
+    float p1 = (VPL == 1 || (NORM && !sel1)) ? 0.f : expf(x1 - m);
+    const float rz = 1.0f / group_sum<LPT>(p0 + p1);
+    p0 *= rz;
+    p1 *= rz;
+    const float dot = group_sum<LPT>(p0 * g0 + p1 * g1);
+    if (!live) continue;
+    const short d0 = f2bf(p0 * (g0 - dot));
+    if constexpr (VPL == 2) {
+      const short d1 = f2bf(p1 * (g1 - dot));
+      *reinterpret_cast<uint32_t*>(dlogits + t * E + e0) =
+          (uint32_t)(uint16_t)d0 | ((uint32_t)(uint16_t)d1 << 16);
+    } else {
+      dlogits[t * E + e0] = d0;
+    }
+  }
+}
+
+static inline int mr_grid(int64_t T, int E) {
+  const int tpw = E < WAVE ? WAVE / E : 1;
+  const int64_t per_block = (int64_t)MR_WAVES * tpw;
+  const int64_t want = (T + per_block - 1) / per_block;
+  return (int)(want < 1 ? 1 : want < MR_GRID_CAP ? want : MR_GRID_CAP);
+}
+
+#define MR_DISPATCH(KERNEL, ...)                                            \
+  do {                                                                      \
+    const dim3 grid(mr_grid(T, E)), block(256);                             \
+    switch (E * 2 + (norm ? 1 : 0)) {                                       \
+      case 17: hipLaunchKernelGGL((KERNEL<8, true>), grid, block, 0, s, __VA_ARGS__); break;    \
+      case 16: hipLaunchKernelGGL((KERNEL<8, false>), grid, block, 0, s, __VA_ARGS__); break;   \
+      case 33: hipLaunchKernelGGL((KERNEL<16, true>), grid, block, 0, s, __VA_ARGS__); break;   \
+      case 32: hipLaunchKernelGGL((KERNEL<16, false>), grid, block, 0, s, __VA_ARGS__); break;  \
+      case 65: hipLaunchKernelGGL((KERNEL<32, true>), grid, block, 0, s, __VA_ARGS__); break;   \
+      case 64: hipLaunchKernelGGL((KERNEL<32, false>), grid, block, 0, s, __VA_ARGS__); break;  \
+      case 129: hipLaunchKernelGGL((KERNEL<64, true>), grid, block, 0, s, __VA_ARGS__); break;  \
+      case 128: hipLaunchKernelGGL((KERNEL<64, false>), grid, block, 0, s, __VA_ARGS__); break; \
+      case 257: hipLaunchKernelGGL((KERNEL<128, true>), grid, block, 0, s, __VA_ARGS__); break; \
+      case 256: hipLaunchKernelGGL((KERNEL<128, false>), grid, block, 0, s, __VA_ARGS__); break;\
+      default: break; /* the binding rejects every other E */               \
+    }                                                                       \
+  } while (0)
+
+extern "C" {
+void moe_router_fwd_launch(const void* logits, int* topk_idx, float* topk_w,
+                           int64_t T, int E, int k, int norm, hipStream_t s) {
+  if (T < 1) return;
+  MR_DISPATCH(moe_router_fwd_kernel, (const short*)logits, topk_idx, topk_w,
+              T, k);
+}
+
+void moe_router_bwd_launch(const void* logits, const int* topk_idx,
+                           const float* d_topk_w, void* dlogits, int64_t T,
+                           int E, int k, int norm, hipStream_t s) {
+  if (T < 1) return;
+  MR_DISPATCH(moe_router_bwd_kernel, (const short*)logits, topk_idx, d_topk_w,
+              (short*)dlogits, T, k);
+}
+}

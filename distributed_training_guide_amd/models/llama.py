@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import (RMSNorm, causal_lm_loss, doc_bounds, flash_attention,
-                   qkv_norm_rope, qkv_rope, silu_mul)
+                   moe_mlp, qkv_norm_rope, qkv_rope, silu_mul)
 from ..ops.embedding import Embedding
 from ..ops.fused_linear_ce import fused_causal_lm_loss
 from ..ops.rmsnorm import add_rmsnorm
@@ -51,6 +51,14 @@ class LlamaConfig:
     # explicit head dim for models that decouple it from hidden / heads
     # (Qwen3 uses 128 throughout); None = hidden_size // num_attention_heads
     head_dim_override: int | None = None
+    # mixture of experts (Qwen3-MoE): num_experts > 0 replaces every layer's
+    # dense MLP by num_experts SwiGLU experts of moe_intermediate_size, each
+    # token routed to num_experts_per_tok of them; norm_topk_prob
+    # renormalises the router's softmax over the selected experts
+    num_experts: int = 0
+    num_experts_per_tok: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = True
 
     @property
     def head_dim(self) -> int:
@@ -71,6 +79,8 @@ class LlamaConfig:
         if self.qk_norm:
             attn += 2 * d
         mlp = 3 * h * i
+        if self.num_experts > 0:  # the experts and the router
+            mlp = self.num_experts * (3 * h * self.moe_intermediate_size + h)
         per_layer = attn + mlp + 2 * h
         embed = v * h * (1 if self.tie_word_embeddings else 2)
         return per_layer * self.num_hidden_layers + embed + h
@@ -138,6 +148,36 @@ class LlamaMLP(nn.Module):
         return self.down_proj(silu_mul(self.gate_up_proj(x)))
 
 
+class LlamaMoE(nn.Module):
+    """Mixture-of-experts feed-forward (ops/moe.py): a bias-free router and
+    the experts' weights as two 3-D parameters, gate|up packed per expert
+    like LlamaMLP's.  The router's weight goes to the op directly and
+    convert_linears_to_fp8 skips modules named `router`, so the router GEMM
+    is bf16 and is reported as such."""
+
+    def __init__(self, config: LlamaConfig, device=None, dtype=None):
+        super().__init__()
+        h, i, e = (config.hidden_size, config.moe_intermediate_size,
+                   config.num_experts)
+        if not 1 <= config.num_experts_per_tok <= e:
+            raise ValueError(
+                f"num_experts_per_tok must be in [1, {e}], got "
+                f"{config.num_experts_per_tok}")
+        self.top_k = config.num_experts_per_tok
+        self.norm_topk_prob = config.norm_topk_prob
+        self.router = nn.Linear(h, e, bias=False, device=device, dtype=dtype)
+        self.gate_up_proj = nn.Parameter(
+            torch.empty(e, 2 * i, h, device=device, dtype=dtype))
+        self.down_proj = nn.Parameter(
+            torch.empty(e, h, i, device=device, dtype=dtype))
+
+    def forward(self, x):
+        y = moe_mlp(x.reshape(-1, x.shape[-1]), self.router.weight,
+                    self.gate_up_proj, self.down_proj, self.top_k,
+                    self.norm_topk_prob)
+        return y.view(x.shape)
+
+
 class LlamaDecoderLayer(nn.Module):
     def __init__(self, config: LlamaConfig, device=None, dtype=None):
         super().__init__()
@@ -146,7 +186,8 @@ class LlamaDecoderLayer(nn.Module):
         self.self_attn = LlamaAttention(config, device, dtype)
         self.post_attention_layernorm = RMSNorm(
             config.hidden_size, config.rms_norm_eps, device, dtype)
-        self.mlp = LlamaMLP(config, device, dtype)
+        mlp_cls = LlamaMoE if config.num_experts > 0 else LlamaMLP
+        self.mlp = mlp_cls(config, device, dtype)
 
     def forward(self, x, position_ids=None, residual=None, doc=None):
         """Two call forms (both via __call__ so FSDP/checkpoint hooks fire):
@@ -218,6 +259,10 @@ class LlamaForCausalLM(nn.Module):
                 m.bias.zero_()
         elif isinstance(m, RMSNorm):
             m.reset_parameters()
+        elif isinstance(m, LlamaMoE):  # the router is an nn.Linear (above)
+            for p in (m.gate_up_proj, m.down_proj):
+                if not p.is_meta:
+                    p.normal_(0.0, std)
 
     def forward(self, input_ids, labels=None, attention_mask=None,
                 position_ids=None, doc_start=None, **_):

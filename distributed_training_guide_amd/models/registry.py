@@ -40,6 +40,18 @@ _QWEN3_DEBUG = dict(vocab_size=1024, rope_theta=1e6, rms_norm_eps=1e-6,
                     max_position_embeddings=2048)
 _QWEN3_CONFIGS["qwen3-debug"] = (256, 688, 4, 4, 2, False)
 
+# Qwen3 mixture-of-experts models: the dense rows' attention (QK-norm,
+# head_dim 128), every layer's MLP replaced by routed experts with
+# norm_topk_prob, no shared expert (the published model cards' values)
+_QWEN3_MOE_CONFIGS = {
+    # name -> (hidden, layers, heads, kv_heads, moe intermediate, experts,
+    #          top-k)
+    "qwen3-30b-a3b": (2048, 48, 32, 4, 768, 128, 8),
+    "qwen3-235b-a22b": (4096, 94, 64, 4, 1536, 128, 8),
+    # small config for tests
+    "qwen3-moe-debug": (256, 2, 4, 2, 128, 8, 2),
+}
+
 _GPT2_CONFIGS = {
     # name -> (hidden, layers, heads); head_dim is 64 throughout
     "gpt2": (768, 12, 12),
@@ -70,6 +82,9 @@ for _name in _QWEN3_CONFIGS:
     if _name != "qwen3-debug":
         _ALIASES[f"qwen/{_name}"] = _name
         _ALIASES[f"qwen/{_name}-base"] = _name
+for _name in ("qwen3-30b-a3b", "qwen3-235b-a22b"):
+    _ALIASES[f"qwen/{_name}"] = _name
+_ALIASES["qwen/qwen3-30b-a3b-base"] = "qwen3-30b-a3b"
 
 
 def resolve_name(name: str) -> str:
@@ -100,10 +115,19 @@ def get_config(name: str):
             num_attention_heads=hq, num_key_value_heads=hkv,
             tie_word_embeddings=tied, qk_norm=True, head_dim_override=128,
             **common)
+    if key in _QWEN3_MOE_CONFIGS:
+        h, L, hq, hkv, mi, ne, topk = _QWEN3_MOE_CONFIGS[key]
+        common = _QWEN3_DEBUG if key == "qwen3-moe-debug" else _QWEN3_COMMON
+        return LlamaConfig(
+            hidden_size=h, intermediate_size=mi, num_hidden_layers=L,
+            num_attention_heads=hq, num_key_value_heads=hkv,
+            tie_word_embeddings=False, qk_norm=True, head_dim_override=128,
+            num_experts=ne, num_experts_per_tok=topk,
+            moe_intermediate_size=mi, norm_topk_prob=True, **common)
     raise ValueError(
         f"unknown model {name!r}; known: "
         f"{', '.join(_GPT2_CONFIGS)}, {', '.join(_LLAMA_CONFIGS)}, "
-        f"{', '.join(_QWEN3_CONFIGS)}")
+        f"{', '.join(_QWEN3_CONFIGS)}, {', '.join(_QWEN3_MOE_CONFIGS)}")
 
 
 def build_model(name_or_config, device=None, dtype=None):

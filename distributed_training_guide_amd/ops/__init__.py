@@ -9,6 +9,8 @@ from .fp8_linear import (Fp8Linear, convert_linears_to_fp8, fp8_linear,
 from .fused_linear_ce import fused_causal_lm_loss
 from .grad_clip import clip_grad_norm_, grad_sq_sum
 from .layernorm import LayerNorm, gelu
+from .moe import (moe_combine, moe_dispatch_index, moe_mlp, moe_router,
+                  moe_scatter)
 from .qk_norm import qkv_norm_rope
 from .rmsnorm import RMSNorm, rmsnorm
 from .rope import qkv_rope, rope
@@ -34,6 +36,11 @@ __all__ = [
     "grad_sq_sum",
     "LayerNorm",
     "gelu",
+    "moe_combine",
+    "moe_dispatch_index",
+    "moe_mlp",
+    "moe_router",
+    "moe_scatter",
     "RMSNorm",
     "rmsnorm",
     "qkv_norm_rope",

@@ -148,7 +148,7 @@ class Fp8Linear(nn.Linear):
         return fp8_linear(x, self.weight)
 
 
-def convert_linears_to_fp8(model, skip=("lm_head",)):
+def convert_linears_to_fp8(model, skip=("lm_head", "router")):
     """Turn the model's eligible nn.Linear modules into Fp8Linear in place
     (the class is swapped, nothing else: parameters, names, state_dict keys
     and optimizer state are untouched, checkpoints stay interchangeable with

@@ -1,0 +1,281 @@
+"""Mixture-of-experts ops: fused top-k router (moe_router.hip), the
+expert-sorted token layout and its row movers (moe_dispatch.hip) on GPU,
+eager torch on CPU.
+
+The rule of ops/fp8_linear.py holds here too: the GEMMs stay with the vendor
+library (the router projection is a plain matmul, the expert GEMMs are
+torch's grouped GEMM with device-side group offsets), and the memory-bound
+work around them is hand-written HIP: softmax -> top-k -> renormalise, the
+expert-sorted layout, the row scatter into it and the k-way weighted combine
+back, each with its backward.  No host sync, no atomics (so no
+non-deterministic index_add_), no cleared buffers.
+
+Layout.  Slot s = t*k + j is token t's j-th selected expert.  `dest[s]` is
+the slot's row in the expert-sorted layout (rows of one expert contiguous,
+ordered by s: the stable sort by expert) and `offs[e]` the inclusive
+cumulative row count per expert, the format F.grouped_mm takes.
+
+The router weights stay f32 until the combine, which rounds once; HF's
+Qwen3MoE rounds them to the activation dtype first.
+
+Not done: expert parallelism, capacity limits / token dropping, the
+load-balancing auxiliary loss, shared experts."""
+import warnings
+
+import torch
+import torch.nn.functional as F
+
+from .._ext import ext, use_hip
+from .swiglu import silu_mul
+
+ROUTER_EXPERTS = (8, 16, 32, 64, 128)
+MAX_TOP_K = 8
+
+
+# --------------------------------------------------------------------------
+# router
+# --------------------------------------------------------------------------
+class _RouterFn(torch.autograd.Function):
+    """Saves the logits and the selection; the probabilities are recomputed
+    in the backward."""
+
+    @staticmethod
+    def forward(ctx, logits, k, norm):
+        idx, w = ext().moe_router_fwd(logits, k, norm)
+        ctx.save_for_backward(logits, idx)
+        ctx.norm = norm
+        ctx.mark_non_differentiable(idx)
+        return idx, w
+
+    @staticmethod
+    def backward(ctx, _didx, dw):
+        logits, idx = ctx.saved_tensors
+        return ext().moe_router_bwd(logits, idx, dw.contiguous(),
+                                    ctx.norm), None, None
+
+
+def moe_router_eager(logits, k, norm_topk_prob=True):
+    """The router in torch ops, f32, differentiable (any device)."""
+    x = logits.float()
+    # stable descending sort: a tie goes to the lower expert index
+    idx = torch.sort(-x.detach(), dim=-1, stable=True).indices[:, :k]
+    if norm_topk_prob:
+        w = torch.softmax(x.gather(1, idx), dim=-1)
+    else:
+        w = torch.softmax(x, dim=-1).gather(1, idx)
+    return idx.to(torch.int32), w
+
+
+def moe_router(logits, k, norm_topk_prob=True):
+    """Top-k routing over router logits [T, E] (bf16 on the GPU).
+
+    Returns (topk_idx int32 [T, k], topk_w f32 [T, k]).  The selection runs
+    on the logits widened to f32, in descending order, a tie going to the
+    lower expert index (the first k of a stable descending sort).  With
+    norm_topk_prob (Qwen3-MoE) the weights are the softmax over the k
+    selected logits, otherwise the full softmax's values at the selection.
+    All arithmetic is f32 and the weights are returned in f32.
+
+    On the GPU E must be one of ROUTER_EXPERTS and 1 <= k <= min(8, E)."""
+    T, E = logits.shape
+    if not 1 <= k <= E:
+        raise ValueError(f"moe_router: k must be in [1, {E}], got {k}")
+    if use_hip(logits):
+        if E not in ROUTER_EXPERTS or k > MAX_TOP_K:
+            raise ValueError(
+                f"moe_router: the GPU kernel takes E in {ROUTER_EXPERTS} and "
+                f"k <= {MAX_TOP_K}, got E={E}, k={k}")
+        return _RouterFn.apply(logits.contiguous(), int(k),
+                               bool(norm_topk_prob))
+    return moe_router_eager(logits, k, norm_topk_prob)
+
+
+# --------------------------------------------------------------------------
+# expert-sorted layout
+# --------------------------------------------------------------------------
+def moe_dispatch_index_eager(topk_idx, num_experts):
+    """(dest, offs) by a stable sort (any device)."""
+    flat = topk_idx.reshape(-1).long()
+    order = torch.sort(flat, stable=True).indices
+    dest = torch.empty_like(order)
+    dest[order] = torch.arange(flat.numel(), device=flat.device)
+    offs = torch.bincount(flat, minlength=num_experts).cumsum(0)
+    return dest.to(torch.int32), offs.to(torch.int32)
+
+
+def moe_dispatch_index(topk_idx, num_experts):
+    """Expert-sorted layout of the slots of topk_idx [T, k] (values in
+    [0, num_experts)): (dest int32 [T*k], offs int32 [num_experts]).
+
+    dest[t*k + j] is the slot's row; rows of one expert are contiguous and
+    ordered by slot.  offs is the inclusive cumulative row count per expert.
+    Built on the device without a host sync or atomics; bitwise
+    reproducible.  Carries no gradient."""
+    if use_hip(topk_idx):
+        dest, offs = ext().moe_dispatch_index(
+            topk_idx.to(torch.int32).contiguous(), int(num_experts))
+        return dest, offs
+    return moe_dispatch_index_eager(topk_idx, num_experts)
+
+
+class _ScatterFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dest, k):
+        ctx.save_for_backward(dest)
+        ctx.k = k
+        return ext().moe_scatter(x, dest)
+
+    @staticmethod
+    def backward(ctx, dxp):
+        (dest,) = ctx.saved_tensors
+        # dx[t] = sum_j dxp[dest[t*k + j]]: the combine with weights of one
+        return ext().moe_combine(dxp.contiguous(), dest, None, ctx.k), \
+            None, None
+
+
+def _rows_of(dest, k):
+    """token of every row of the sorted layout (the inverse of dest, / k)"""
+    inv = torch.empty_like(dest, dtype=torch.long)
+    inv[dest.long()] = torch.arange(dest.numel(), device=dest.device)
+    return inv, torch.div(inv, k, rounding_mode="floor")
+
+
+def moe_scatter_eager(x, dest, k):
+    return x.index_select(0, _rows_of(dest, k)[1])
+
+
+def moe_scatter(x, dest, k):
+    """xp [T*k, H] with xp[dest[t*k + j]] = x[t] for every slot: the tokens
+    in expert-sorted order, each row a bit-exact copy.  x is [T, H] (bf16
+    with H % 8 == 0 on the GPU); dest must be a permutation of [0, T*k)."""
+    if dest.numel() != x.shape[0] * k:
+        raise ValueError("moe_scatter: dest must hold k slots per row of x")
+    if use_hip(x):
+        return _ScatterFn.apply(x.contiguous(), dest, int(k))
+    return moe_scatter_eager(x, dest, k)
+
+
+class _CombineFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, yp, dest, w):
+        ctx.save_for_backward(yp, dest, w)
+        return ext().moe_combine(yp, dest, w, w.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        yp, dest, w = ctx.saved_tensors
+        # one pass: dyp[dest[s]] = w[s] * dy[t] and dw[s] = <dy[t], yp[..]>
+        dyp, dw = ext().moe_combine_bwd(dy.contiguous(), dest, w, yp)
+        return dyp, None, dw
+
+
+def moe_combine_eager(yp, dest, w):
+    """The classic chain: weigh the sorted rows, index_add_ them into an f32
+    accumulator per token, round once."""
+    T, k = w.shape
+    inv, tok = _rows_of(dest, k)
+    rows = yp.float() * w.reshape(-1)[inv].unsqueeze(1)
+    y = torch.zeros(T, yp.shape[1], dtype=torch.float32, device=yp.device)
+    return y.index_add(0, tok, rows).to(yp.dtype)
+
+
+def moe_combine(yp, dest, w):
+    """y [T, H] = sum_j w[t, j] * yp[dest[t*k + j]]: the experts' outputs
+    back in token order, accumulated in f32 in fixed j order and rounded
+    once.  yp is [T*k, H], w f32 [T, k]."""
+    if w.dim() != 2 or dest.numel() != w.numel() \
+            or yp.shape[0] != dest.numel():
+        raise ValueError("moe_combine: yp [T*k, H], dest [T*k], w [T, k]")
+    if use_hip(yp):
+        return _CombineFn.apply(yp.contiguous(), dest,
+                                w.float().contiguous())
+    return moe_combine_eager(yp, dest, w)
+
+
+# --------------------------------------------------------------------------
+# expert GEMMs and the composed layer
+# --------------------------------------------------------------------------
+# "grouped" or "loop": which path the last expert_mm call took (reporting
+# only; the decision is kept per device type in _grouped_mm_works)
+last_expert_mm_path = None
+_grouped_mm_works = {}  # device type -> bool, decided by the first call
+
+
+def _expert_mm_loop(a, weight, offs):
+    lo, parts = 0, []
+    for e, hi in enumerate(offs.tolist()):  # one host read
+        parts.append(F.linear(a[lo:hi], weight[e]))
+        lo = hi
+    return torch.cat(parts)
+
+
+def expert_mm(a, weight, offs):
+    """Rows [offs[e-1], offs[e]) of a [N, K] times weight[e].T, for weight
+    [E, M, K]: the one helper both expert GEMMs go through.  torch's grouped
+    GEMM takes the device-side offsets, so nothing waits on the host.
+
+    Where this build of torch cannot run the grouped GEMM on a's kind of
+    device, the helper warns once and from then on loops over the experts'
+    row slices on that kind of device, at the cost of one host read of offs
+    per call.  Only the first call on a device type decides, and only a
+    refusal decides: the arguments are checked here first, so a caller's
+    shape error is a ValueError, and running out of memory is re-raised."""
+    global last_expert_mm_path
+    if a.dim() != 2 or weight.dim() != 3 or a.shape[1] != weight.shape[2] \
+            or offs.shape != (weight.shape[0],) or offs.dtype != torch.int32:
+        raise ValueError(
+            f"expert_mm: a [N, K], weight [E, M, K], offs int32 [E]; got "
+            f"{tuple(a.shape)}, {tuple(weight.shape)}, {tuple(offs.shape)} "
+            f"{offs.dtype}")
+    kind = a.device.type
+    if _grouped_mm_works.get(kind, True):
+        try:
+            out = F.grouped_mm(a, weight.transpose(-2, -1), offs=offs)
+            _grouped_mm_works[kind] = True
+            last_expert_mm_path = "grouped"
+            return out
+        except torch.OutOfMemoryError:
+            raise
+        except (RuntimeError, NotImplementedError) as e:
+            if _grouped_mm_works.get(kind):
+                raise  # it has worked here before: an error of this call
+            _grouped_mm_works[kind] = False
+            warnings.warn(
+                f"F.grouped_mm is not usable on {kind} in this torch build "
+                f"({e}); the expert GEMMs fall back to a per-expert loop "
+                "with one host sync per call", RuntimeWarning, stacklevel=2)
+    last_expert_mm_path = "loop"
+    return _expert_mm_loop(a, weight, offs)
+
+
+def _mlp_chain(x, router_weight, gate_up, down, k, norm, router, index,
+               scatter, combine):
+    E = gate_up.shape[0]
+    idx, w = router(F.linear(x, router_weight), k, norm)
+    dest, offs = index(idx, E)
+    xp = scatter(x, dest, k)
+    h = silu_mul(expert_mm(xp, gate_up, offs))
+    return combine(expert_mm(h, down, offs), dest, w)
+
+
+def moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob=True):
+    """moe_mlp as the torch-op chain (stable sort, index_select, the same
+    GEMM helper, index_add_ in f32), on any device: the CPU path, and what
+    the fused path is compared and benchmarked against."""
+    return _mlp_chain(x, router_weight, gate_up, down, k, norm_topk_prob,
+                      moe_router_eager, moe_dispatch_index_eager,
+                      moe_scatter_eager, moe_combine_eager)
+
+
+def moe_mlp(x, router_weight, gate_up, down, k, norm_topk_prob=True):
+    """A mixture-of-experts SwiGLU feed-forward over tokens x [T, H].
+
+    router_weight [E, H]; gate_up [E, 2I, H] (gate | up packed, so silu_mul
+    serves the activation on the sorted rows); down [E, H, I].  Every token
+    goes through its k routed experts and the outputs are summed with the
+    router's weights."""
+    if use_hip(x):
+        return _mlp_chain(x, router_weight, gate_up, down, k, norm_topk_prob,
+                          moe_router, moe_dispatch_index, moe_scatter,
+                          moe_combine)
+    return moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob)

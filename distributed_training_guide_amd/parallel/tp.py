@@ -330,6 +330,12 @@ class TPLlamaForCausalLM(nn.Module):
     def __init__(self, config: LlamaConfig, mesh, device=None, dtype=None,
                  loss_parallel=False):
         super().__init__()
+        if getattr(config, "num_experts", 0) > 0:
+            raise ValueError(
+                "tensor parallelism does not support mixture-of-experts "
+                f"configs (num_experts={config.num_experts}): the experts "
+                "are not sharded and expert parallelism is not implemented; "
+                "use the single, DDP or FSDP strategy")
         self.config = config
         self.mesh = mesh
         self.loss_parallel = loss_parallel

@@ -116,10 +116,12 @@ def check_fp8_supported(config, strategy):
 
 def apply_fp8(model):
     """Convert the Llama projections (qkv_proj, o_proj, gate_up_proj,
-    down_proj) to FP8 linears in place; lm_head and embeddings stay bf16."""
+    down_proj) to FP8 linears in place; lm_head and embeddings stay bf16,
+    and so does a mixture-of-experts layer (its router is skipped by name,
+    its experts are 3-D parameters, not linears)."""
     from .ops import convert_linears_to_fp8
 
-    names = convert_linears_to_fp8(model, skip=("lm_head",))
+    names = convert_linears_to_fp8(model, skip=("lm_head", "router"))
     if not names:
         raise ValueError("--fp8: the model has no bias-free linear with "
                          "dimensions that are multiples of 16 to convert")

@@ -125,7 +125,10 @@ def analyze(src, loops=False):
         asm = Path(tmp) / "out.s"
         cmd = ["hipcc", "--offload-device-only", "-S", str(src), "-o",
                str(asm), "-Rpass-analysis=kernel-resource-usage"]
-        r = subprocess.run(cmd + device_flags(), text=True,
+        sys.path.insert(0, str(Path(__file__).resolve().parent))
+        from build_hip import file_flags  # the build's per-file flags
+
+        r = subprocess.run(cmd + device_flags() + file_flags(src), text=True,
                            capture_output=True)
         if r.returncode:
             sys.stderr.write(r.stderr)
