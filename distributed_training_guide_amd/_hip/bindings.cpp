@@ -438,6 +438,60 @@ torch::Tensor moe_router_bwd(torch::Tensor logits, torch::Tensor topk_idx,
   return dlogits;
 }
 
+// (topk_idx, topk_w, counts int32 [E], aux, z): the router with the
+// load-balancing loss and the z-loss of its T >= 1 tokens as 0-dim f32
+std::vector<torch::Tensor> moe_router_aux_fwd(torch::Tensor logits, int64_t k,
+                                              bool norm) {
+  moe_router_check(logits, k);
+  const int64_t T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(T >= 1 && T <= INT32_MAX,
+              "moe_router_aux: T must be in [1, 2^31), got ", T);
+  auto idx = torch::empty({T, k}, logits.options().dtype(torch::kInt));
+  auto fopt = logits.options().dtype(torch::kFloat);
+  auto w = torch::empty({T, k}, fopt);
+  auto counts = torch::empty({E}, logits.options().dtype(torch::kInt));
+  auto aux = torch::empty({}, fopt);
+  auto z = torch::empty({}, fopt);
+  auto partials =
+      torch::empty({moe_router_aux_grid(T, (int)E), 2 * E + 1}, fopt);
+  moe_router_aux_fwd_launch(logits.data_ptr(), idx.data_ptr<int>(),
+                            w.data_ptr<float>(), partials.data_ptr<float>(),
+                            counts.data_ptr<int>(), aux.data_ptr<float>(),
+                            z.data_ptr<float>(), T, (int)E, (int)k,
+                            norm ? 1 : 0, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {idx, w, counts, aux, z};
+}
+
+torch::Tensor moe_router_aux_bwd(torch::Tensor logits, torch::Tensor topk_idx,
+                                 torch::Tensor d_topk_w, torch::Tensor counts,
+                                 torch::Tensor g_aux, torch::Tensor g_z,
+                                 bool norm) {
+  TORCH_CHECK(topk_idx.dim() == 2, "topk_idx must be [T, k]");
+  const int64_t k = topk_idx.size(1);
+  moe_router_check(logits, k);
+  const int64_t T = logits.size(0), E = logits.size(1);
+  CHECK_ON_DEVICE_CONTIG(topk_idx, logits, torch::kInt, "int32");
+  CHECK_ON_DEVICE_CONTIG(d_topk_w, logits, torch::kFloat, "f32");
+  CHECK_ON_DEVICE_CONTIG(counts, logits, torch::kInt, "int32");
+  CHECK_ON_DEVICE_CONTIG(g_aux, logits, torch::kFloat, "f32");
+  CHECK_ON_DEVICE_CONTIG(g_z, logits, torch::kFloat, "f32");
+  TORCH_CHECK(topk_idx.size(0) == T && d_topk_w.sizes() == topk_idx.sizes(),
+              "topk_idx and d_topk_w must be [T, k] with the logits' T");
+  TORCH_CHECK(counts.dim() == 1 && counts.size(0) == E,
+              "counts must be [E]");
+  TORCH_CHECK(g_aux.numel() == 1 && g_z.numel() == 1,
+              "g_aux and g_z must hold one element each");
+  auto dlogits = torch::empty_like(logits);
+  moe_router_aux_bwd_launch(logits.data_ptr(), topk_idx.data_ptr<int>(),
+                            d_topk_w.data_ptr<float>(),
+                            counts.data_ptr<int>(), g_aux.data_ptr<float>(),
+                            g_z.data_ptr<float>(), dlogits.data_ptr(), T,
+                            (int)E, (int)k, norm ? 1 : 0, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dlogits;
+}
+
 // (dest [T*k], offs [E]): views of one int32 buffer whose tail is the index
 // build's scratch
 std::vector<torch::Tensor> moe_dispatch_index(torch::Tensor topk_idx,
@@ -961,6 +1015,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qkv_norm_rope_bwd", &qkv_norm_rope_bwd);
   m.def("moe_router_fwd", &moe_router_fwd);
   m.def("moe_router_bwd", &moe_router_bwd);
+  m.def("moe_router_aux_fwd", &moe_router_aux_fwd);
+  m.def("moe_router_aux_bwd", &moe_router_aux_bwd);
   m.def("moe_dispatch_index", &moe_dispatch_index);
   m.def("moe_scatter", &moe_scatter);
   m.def("moe_combine", &moe_combine);

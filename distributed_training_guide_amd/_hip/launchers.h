@@ -92,6 +92,24 @@ void moe_router_bwd_launch(const void* logits, const int* topk_idx,
                            const float* d_topk_w, void* dlogits, int64_t T,
                            int E, int k, int norm, hipStream_t s);
 
+// moe_router_aux.hip: the same router, which also produces the
+// load-balancing loss `aux` and the router z-loss `z` of the T >= 1 tokens
+// (two f32 scalars) and counts int32 [E], the slots routed to each expert.
+// topk_idx and topk_w are moe_router_fwd_launch's bits.  `partials` is
+// moe_router_aux_grid(T, E) * (2E + 1) f32 of scratch that needs no
+// initialisation.  The backward adds the two losses' terms to the routing
+// term; g_aux and g_z are the upstream gradients as device scalars.
+int moe_router_aux_grid(int64_t T, int E);
+void moe_router_aux_fwd_launch(const void* logits, int* topk_idx,
+                               float* topk_w, float* partials, int* counts,
+                               float* aux, float* z, int64_t T, int E, int k,
+                               int norm, hipStream_t s);
+void moe_router_aux_bwd_launch(const void* logits, const int* topk_idx,
+                               const float* d_topk_w, const int* counts,
+                               const float* g_aux, const float* g_z,
+                               void* dlogits, int64_t T, int E, int k,
+                               int norm, hipStream_t s);
+
 // moe_dispatch.hip.  moe_index_launch turns topk_idx (N = T*k slots, values
 // in [0, E)) into dest int32 [N] (the slot's row in the expert-sorted
 // layout) and offs int32 [E] (inclusive cumulative rows per expert); `hist`

@@ -59,6 +59,16 @@ class LlamaConfig:
     num_experts_per_tok: int = 0
     moe_intermediate_size: int = 0
     norm_topk_prob: bool = True
+    # router regularisers (ops/moe.py): the loss gains
+    # router_aux_loss_coef * mean over layers of the load-balancing loss (HF
+    # trains Qwen3-MoE with 0.001) and router_z_loss_coef * mean over layers
+    # of the router z-loss.  With both 0 the router is called without them.
+    router_aux_loss_coef: float = 0.0
+    router_z_loss_coef: float = 0.0
+
+    @property
+    def router_losses(self) -> bool:
+        return self.router_aux_loss_coef != 0 or self.router_z_loss_coef != 0
 
     @property
     def head_dim(self) -> int:
@@ -90,6 +100,9 @@ class LlamaConfig:
 class CausalLMOutput:
     loss: torch.Tensor | None = None
     logits: torch.Tensor | None = None
+    # means over the MoE layers, set when the config asks for router losses
+    router_aux_loss: torch.Tensor | None = None
+    router_z_loss: torch.Tensor | None = None
 
 
 class LlamaAttention(nn.Module):
@@ -165,6 +178,12 @@ class LlamaMoE(nn.Module):
                 f"{config.num_experts_per_tok}")
         self.top_k = config.num_experts_per_tok
         self.norm_topk_prob = config.norm_topk_prob
+        # (aux, z) of the latest forward.  One attribute, overwritten every
+        # forward: the model reads it right after the layer loop, so the
+        # loss is built on the graph of that forward, and a checkpoint
+        # recompute during backward only replaces what was already used.
+        self.router_losses = config.router_losses
+        self.aux_losses = None
         self.router = nn.Linear(h, e, bias=False, device=device, dtype=dtype)
         self.gate_up_proj = nn.Parameter(
             torch.empty(e, 2 * i, h, device=device, dtype=dtype))
@@ -172,9 +191,14 @@ class LlamaMoE(nn.Module):
             torch.empty(e, h, i, device=device, dtype=dtype))
 
     def forward(self, x):
-        y = moe_mlp(x.reshape(-1, x.shape[-1]), self.router.weight,
-                    self.gate_up_proj, self.down_proj, self.top_k,
-                    self.norm_topk_prob)
+        tokens = x.reshape(-1, x.shape[-1])
+        if self.router_losses:
+            y, *self.aux_losses = moe_mlp(
+                tokens, self.router.weight, self.gate_up_proj,
+                self.down_proj, self.top_k, self.norm_topk_prob, aux=True)
+        else:
+            y = moe_mlp(tokens, self.router.weight, self.gate_up_proj,
+                        self.down_proj, self.top_k, self.norm_topk_prob)
         return y.view(x.shape)
 
 
@@ -296,15 +320,29 @@ class LlamaForCausalLM(nn.Module):
             for layer in self.layers:
                 x = layer(x, position_ids, doc=doc)
             x = self.norm(x)
+        aux = z = None
+        if self.config.router_losses and self.config.num_experts > 0:
+            # each layer's (aux, z) from the forward that just ran, averaged
+            per_layer = [layer.mlp.aux_losses for layer in self.layers]
+            aux = torch.stack([a for a, _ in per_layer]).mean()
+            z = torch.stack([b for _, b in per_layer]).mean()
         if labels is not None and x.is_cuda:
             # chunked fused projection+CE: the [B,S,V] logits (+grad) are
             # never materialized (ops/fused_linear_ce.py) — logits=None,
             # like the reference's loss-only training consumers (02:149-163
             # only reads outputs.loss)
             loss = fused_causal_lm_loss(x, self.lm_head.weight, labels)
-            return CausalLMOutput(loss=loss, logits=None)
+            return CausalLMOutput(self._with_router_losses(loss, aux, z),
+                                  None, aux, z)
         logits = self.lm_head(x)
         loss = None
         if labels is not None:
-            loss = causal_lm_loss(logits, labels)
-        return CausalLMOutput(loss=loss, logits=logits)
+            loss = self._with_router_losses(causal_lm_loss(logits, labels),
+                                            aux, z)
+        return CausalLMOutput(loss, logits, aux, z)
+
+    def _with_router_losses(self, loss, aux, z):
+        if aux is None:
+            return loss
+        return loss + self.config.router_aux_loss_coef * aux \
+            + self.config.router_z_loss_coef * z

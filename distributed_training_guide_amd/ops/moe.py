@@ -18,8 +18,19 @@ cumulative row count per expert, the format F.grouped_mm takes.
 The router weights stay f32 until the combine, which rounds once; HF's
 Qwen3MoE rounds them to the activation dtype first.
 
-Not done: expert parallelism, capacity limits / token dropping, the
-load-balancing auxiliary loss, shared experts."""
+Router auxiliary losses (moe_router(..., aux=True), moe_router_aux.hip): the
+load-balancing loss of Switch / HF, aux = E * sum_e (c[e] / T) * P[e] with
+c[e] the slots routed to expert e and P[e] the mean FULL-softmax probability
+of e (in both norm_topk_prob modes), and the router z-loss of ST-MoE,
+z = mean_t logsumexp(x[t])^2, come out of the router kernels with their
+gradients.  Two conventions differ from HF's Qwen3MoE: HF pools the tokens
+of all layers before forming c and P, while here every layer forms its own
+over the T tokens it sees and the model averages the layers' losses (the
+Switch / Megatron convention); and under data parallelism the statistics are
+per rank and per micro-batch, with no collective.
+
+Not done: expert parallelism, capacity limits / token dropping, shared
+experts."""
 import warnings
 
 import torch
@@ -54,8 +65,33 @@ class _RouterFn(torch.autograd.Function):
                                     ctx.norm), None, None
 
 
-def moe_router_eager(logits, k, norm_topk_prob=True):
-    """The router in torch ops, f32, differentiable (any device)."""
+class _RouterAuxFn(torch.autograd.Function):
+    """_RouterFn with the two auxiliary losses as further outputs.  Saves
+    the expert counts as well; a missing upstream gradient counts as zero
+    and the scalars' gradients reach the kernel as device tensors."""
+
+    @staticmethod
+    def forward(ctx, logits, k, norm):
+        idx, w, counts, aux, z = ext().moe_router_aux_fwd(logits, k, norm)
+        ctx.save_for_backward(logits, idx, counts)
+        ctx.norm = norm
+        ctx.mark_non_differentiable(idx)
+        return idx, w, aux, z
+
+    @staticmethod
+    def backward(ctx, _didx, dw, daux, dz):
+        logits, idx, counts = ctx.saved_tensors
+        dw = torch.zeros(idx.shape, dtype=torch.float32,
+                         device=idx.device) if dw is None else dw.contiguous()
+        daux, dz = (logits.new_zeros((), dtype=torch.float32) if g is None
+                    else g.float().contiguous() for g in (daux, dz))
+        return ext().moe_router_aux_bwd(logits, idx, dw, counts, daux, dz,
+                                        ctx.norm), None, None
+
+
+def moe_router_eager(logits, k, norm_topk_prob=True, aux=False):
+    """The router in torch ops, f32, differentiable (any device); with `aux`
+    the two auxiliary losses of moe_router as well."""
     x = logits.float()
     # stable descending sort: a tie goes to the lower expert index
     idx = torch.sort(-x.detach(), dim=-1, stable=True).indices[:, :k]
@@ -63,10 +99,17 @@ def moe_router_eager(logits, k, norm_topk_prob=True):
         w = torch.softmax(x.gather(1, idx), dim=-1)
     else:
         w = torch.softmax(x, dim=-1).gather(1, idx)
-    return idx.to(torch.int32), w
+    if not aux:
+        return idx.to(torch.int32), w
+    T, E = x.shape
+    lse = torch.logsumexp(x, dim=-1)
+    counts = torch.bincount(idx.reshape(-1), minlength=E).to(x.dtype)
+    p_mean = torch.exp(x - lse.unsqueeze(1)).mean(0)
+    return (idx.to(torch.int32), w, E * (counts / T * p_mean).sum(),
+            lse.square().mean())
 
 
-def moe_router(logits, k, norm_topk_prob=True):
+def moe_router(logits, k, norm_topk_prob=True, aux=False):
     """Top-k routing over router logits [T, E] (bf16 on the GPU).
 
     Returns (topk_idx int32 [T, k], topk_w f32 [T, k]).  The selection runs
@@ -76,18 +119,25 @@ def moe_router(logits, k, norm_topk_prob=True):
     selected logits, otherwise the full softmax's values at the selection.
     All arithmetic is f32 and the weights are returned in f32.
 
+    With `aux` it returns (topk_idx, topk_w, aux, z): the load-balancing
+    loss and the router z-loss of these T tokens (the module docstring has
+    the definitions) as 0-dim f32, differentiable; topk_idx and topk_w are
+    the same bits.  The losses always use the full softmax.
+
     On the GPU E must be one of ROUTER_EXPERTS and 1 <= k <= min(8, E)."""
     T, E = logits.shape
     if not 1 <= k <= E:
         raise ValueError(f"moe_router: k must be in [1, {E}], got {k}")
+    if aux and T < 1:
+        raise ValueError("moe_router: the auxiliary losses need a token")
     if use_hip(logits):
         if E not in ROUTER_EXPERTS or k > MAX_TOP_K:
             raise ValueError(
                 f"moe_router: the GPU kernel takes E in {ROUTER_EXPERTS} and "
                 f"k <= {MAX_TOP_K}, got E={E}, k={k}")
-        return _RouterFn.apply(logits.contiguous(), int(k),
-                               bool(norm_topk_prob))
-    return moe_router_eager(logits, k, norm_topk_prob)
+        fn = _RouterAuxFn if aux else _RouterFn
+        return fn.apply(logits.contiguous(), int(k), bool(norm_topk_prob))
+    return moe_router_eager(logits, k, norm_topk_prob, aux)
 
 
 # --------------------------------------------------------------------------
@@ -248,34 +298,42 @@ def expert_mm(a, weight, offs):
     return _expert_mm_loop(a, weight, offs)
 
 
-def _mlp_chain(x, router_weight, gate_up, down, k, norm, router, index,
+def _mlp_chain(x, router_weight, gate_up, down, k, norm, aux, router, index,
                scatter, combine):
     E = gate_up.shape[0]
-    idx, w = router(F.linear(x, router_weight), k, norm)
+    logits = F.linear(x, router_weight)
+    # without aux the router is called exactly as before the option existed
+    idx, w, *losses = router(logits, k, norm, True) if aux \
+        else router(logits, k, norm)
     dest, offs = index(idx, E)
     xp = scatter(x, dest, k)
     h = silu_mul(expert_mm(xp, gate_up, offs))
-    return combine(expert_mm(h, down, offs), dest, w)
+    y = combine(expert_mm(h, down, offs), dest, w)
+    return (y, *losses) if aux else y
 
 
-def moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob=True):
+def moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob=True,
+                  aux=False):
     """moe_mlp as the torch-op chain (stable sort, index_select, the same
     GEMM helper, index_add_ in f32), on any device: the CPU path, and what
     the fused path is compared and benchmarked against."""
-    return _mlp_chain(x, router_weight, gate_up, down, k, norm_topk_prob,
+    return _mlp_chain(x, router_weight, gate_up, down, k, norm_topk_prob, aux,
                       moe_router_eager, moe_dispatch_index_eager,
                       moe_scatter_eager, moe_combine_eager)
 
 
-def moe_mlp(x, router_weight, gate_up, down, k, norm_topk_prob=True):
+def moe_mlp(x, router_weight, gate_up, down, k, norm_topk_prob=True,
+            aux=False):
     """A mixture-of-experts SwiGLU feed-forward over tokens x [T, H].
 
     router_weight [E, H]; gate_up [E, 2I, H] (gate | up packed, so silu_mul
     serves the activation on the sorted rows); down [E, H, I].  Every token
     goes through its k routed experts and the outputs are summed with the
-    router's weights."""
+    router's weights.  With `aux` it returns (y, aux, z), the router's two
+    auxiliary losses over these tokens (moe_router)."""
     if use_hip(x):
         return _mlp_chain(x, router_weight, gate_up, down, k, norm_topk_prob,
-                          moe_router, moe_dispatch_index, moe_scatter,
+                          aux, moe_router, moe_dispatch_index, moe_scatter,
                           moe_combine)
-    return moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob)
+    return moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob,
+                         aux)

@@ -12,9 +12,12 @@ Extras the reference ships as diff-recipes are first-class flags:
 --grad-accum-steps (related-topics/gradient-accumulation, incl. no_sync),
 --deterministic + RNG checkpointing (related-topics/determinism),
 --wandb (wandb-configurations topologies),
---fp8 (FP8 projection GEMMs, ops/fp8_linear.py; Llama, single and DDP).
+--fp8 (FP8 projection GEMMs, ops/fp8_linear.py; Llama, single and DDP),
+--router-aux-loss-coef / --router-z-loss-coef (mixture-of-experts router
+losses, ops/moe.py).
 """
 import argparse
+import dataclasses
 import logging
 import os
 from contextlib import nullcontext
@@ -74,6 +77,13 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
                        help="run the qkv/o/gate_up/down projection GEMMs in "
                             "FP8 (e4m3, tensor-wise dynamic scaling); Llama "
                             "models, single-device and DDP strategies only")
+        p.add_argument("--router-aux-loss-coef", default=0.0, type=float,
+                       help="mixture-of-experts models: weight of the "
+                            "router's load-balancing loss, averaged over "
+                            "the layers (HF trains Qwen3-MoE with 0.001)")
+        p.add_argument("--router-z-loss-coef", default=0.0, type=float,
+                       help="mixture-of-experts models: weight of the "
+                            "router z-loss, averaged over the layers")
         p.add_argument("--deterministic", action="store_true")
         p.add_argument("--wandb", action="store_true")
         p.add_argument("--wandb-mode", default="rank0",
@@ -112,6 +122,23 @@ def check_fp8_supported(config, strategy):
             f"{getattr(config, 'model_type', None)!r}: only Llama models, "
             "whose projections are bias-free, are converted (GPT-2's "
             "linears carry biases)")
+
+
+def apply_router_loss_coefs(config, args):
+    """--router-aux-loss-coef / --router-z-loss-coef: the config with the
+    two fields set; ValueError where a non-zero value has no router to act
+    on (a dense model)."""
+    coefs = dict(
+        router_aux_loss_coef=getattr(args, "router_aux_loss_coef", 0.0),
+        router_z_loss_coef=getattr(args, "router_z_loss_coef", 0.0))
+    if not any(coefs.values()):
+        return config
+    if getattr(config, "num_experts", 0) < 1:
+        raise ValueError(
+            "--router-aux-loss-coef / --router-z-loss-coef need a "
+            f"mixture-of-experts model: {args.model_name} is dense and has "
+            "no router")
+    return dataclasses.replace(config, **coefs)
 
 
 def apply_fp8(model):
@@ -159,7 +186,7 @@ def run_training(args, strategy):
     if getattr(args, "deterministic", False):
         torch.use_deterministic_algorithms(True)
 
-    config = get_config(args.model_name)
+    config = apply_router_loss_coefs(get_config(args.model_name), args)
     if getattr(args, "fp8", False):
         check_fp8_supported(config, strategy)
     model, optimizer, lr_scheduler = strategy.build(config, args)

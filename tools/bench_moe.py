@@ -27,6 +27,12 @@ writes N rows; its backward reads N and writes T; combine forward reads N
 and writes T; combine backward reads T + N and writes N.  The fused ops'
 rates against those floors are reported in TB/s.
 
+--aux times the router with its auxiliary losses instead (moe_router_aux.hip,
+default --out profiles/moe_aux.json), alternating in one run: the plain
+router fwd / bwd of this build, the aux fwd (with its finishing launch) / bwd,
+and the torch-op chain for the same two losses from the logits and the
+selection (logsumexp, exp, bincount, two means) with autograd's backward.
+
 --e2e-layers L additionally times training steps of a cut-down model of the
 same layer shape with L layers (the 30B model's 366 GB of parameter and
 optimizer state do not fit one GPU).  Results go to --out; no threshold is
@@ -121,8 +127,12 @@ def main():
     p.add_argument("--repeats", type=int, default=30)
     p.add_argument("--e2e-layers", type=int, default=0)
     p.add_argument("--e2e-steps", type=int, default=5)
-    p.add_argument("--out", default="profiles/moe.json")
+    p.add_argument("--aux", action="store_true",
+                   help="time the router's auxiliary-loss variants only")
+    p.add_argument("--out", default=None)
     args = p.parse_args()
+    if args.out is None:
+        args.out = "profiles/moe_aux.json" if args.aux else "profiles/moe.json"
 
     if not torch.cuda.is_available():
         sys.exit("bench_moe needs a GPU: timings are not measured on the CPU")
@@ -143,6 +153,7 @@ def main():
     logits = torch.nn.functional.linear(x, router_w)
     dy = torch.randn(T, H, **bf)
     idx, w = C.moe_router_fwd(logits, k, True)
+    idx64 = idx.reshape(-1).long()  # what torch.bincount takes
     dest, offs = C.moe_dispatch_index(idx, E)
     dw = torch.randn(T, k, device=dev)
     yp = torch.randn(N, H, **bf)
@@ -162,6 +173,14 @@ def main():
 
     def t_router(lg):
         return moe.moe_router_eager(lg, k, True)[1]
+
+    def t_aux(lg):
+        """the two losses as torch ops; the selection is given"""
+        xf = lg.float()
+        lse = torch.logsumexp(xf, dim=-1)
+        frac = torch.bincount(idx64, minlength=E).float() / T
+        aux = E * (frac * torch.exp(xf - lse.unsqueeze(1)).mean(0)).sum()
+        return aux + lse.square().mean()
 
     def gemms(xp_, gu_, dn_):
         return moe.expert_mm(silu_mul(moe.expert_mm(xp_, gu_, offs)), dn_,
@@ -202,6 +221,30 @@ def main():
     result = {"tokens": T, "hidden": H, "moe_intermediate": I, "experts": E,
               "top_k": k, "repeats": args.repeats,
               "device": torch.cuda.get_device_name(0)}
+    if args.aux:
+        counts = C.moe_router_aux_fwd(logits, k, True)[2]
+        one = torch.ones((), device=dev)
+        variants = {
+            "router_fwd": variants["router_fwd"],
+            "router_bwd": variants["router_bwd"],
+            "aux_router_fwd": (lambda: C.moe_router_aux_fwd(logits, k, True),
+                               n),
+            "aux_router_bwd": (lambda: C.moe_router_aux_bwd(
+                logits, idx, dw, counts, one, one, True), n),
+            "torch_aux_fwd": (fwd("a", t_aux, logits), n),
+            "torch_aux_bwd": (bwd("a", one), n),
+        }
+        result.update(timed(variants, args.warmup, args.repeats))
+        for pre in ("router", "aux_router", "torch_aux"):
+            result[f"{pre}_fwdbwd_ms"] = round(
+                result[f"{pre}_fwd_ms"] + result[f"{pre}_bwd_ms"], 4)
+        result["aux_over_plain"] = round(
+            result["aux_router_fwdbwd_ms"] / result["router_fwdbwd_ms"], 3)
+        print(json.dumps(result))
+        out = Path(args.out)
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps({"router_aux": result}, indent=2) + "\n")
+        return
     result.update(timed(variants, args.warmup, args.repeats))
     result["expert_gemm_path"] = moe.last_expert_mm_path
     row = H * 2
