@@ -882,6 +882,100 @@ fp8_cast_transpose(torch::Tensor x, torch::Tensor scale, bool rowwise,
   return {q, qt};
 }
 
+// ---------------- fp8 delayed scaling (fp8_delayed.hip) ----------------
+inline void fp8_check_scale(const torch::Tensor& scale,
+                            const torch::Tensor& x) {
+  TORCH_CHECK(scale.is_cuda() && scale.device() == x.device(),
+              "scale must be on the input's device");
+  TORCH_CHECK(scale.dtype() == torch::kFloat && scale.numel() == 1,
+              "scale must be a single f32 value");
+}
+
+inline torch::Tensor fp8_new_partials(const torch::Tensor& x, int64_t R,
+                                      int64_t C) {
+  const int64_t tiles = fp8_tiles((int)R, (int)C);
+  TORCH_CHECK(tiles <= INT32_MAX, "fp8 quantisation: too many tiles");
+  return torch::empty({tiles}, x.options().dtype(torch::kInt));
+}
+
+// fp8_cast_transpose with the scale given, plus the per-tile amax partials
+// (int32: sign-cleared bf16 bit patterns) for fp8_history_update
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
+           torch::Tensor>
+fp8_cast_amax(torch::Tensor x, torch::Tensor scale, bool rowwise,
+              bool transposed) {
+  fp8_check_input(x);
+  TORCH_CHECK(rowwise || transposed,
+              "fp8_cast_amax: ask for at least one output");
+  fp8_check_scale(scale, x);
+  const int64_t R = x.size(0), C = x.size(1);
+  auto opts = x.options().dtype(at::kFloat8_e4m3fn);
+  c10::optional<torch::Tensor> q, qt;
+  if (rowwise) q = torch::empty({R, C}, opts);
+  if (transposed) qt = torch::empty({C, R}, opts);
+  auto partials = fp8_new_partials(x, R, C);
+  fp8_cast_amax_launch(x.data_ptr(), scale.data_ptr<float>(),
+                       q ? q->data_ptr() : nullptr,
+                       qt ? qt->data_ptr() : nullptr, partials.data_ptr(),
+                       (int)R, (int)C, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {q, qt, partials};
+}
+
+// gate_up [R, 2I] bf16 -> (hq [R, I], hqt [I, R], partials) of
+// h = silu(gate) * up, which is never written
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> silu_mul_fp8(
+    torch::Tensor gu, torch::Tensor scale) {
+  CHECK_BF16_CONTIG(gu);
+  TORCH_CHECK(gu.dim() == 2, "silu_mul_fp8 expects gate_up as [R, 2I]");
+  const int64_t R = gu.size(0), I = gu.size(1) / 2;
+  TORCH_CHECK(R > 0 && I > 0 && R % 16 == 0 && gu.size(1) % 32 == 0,
+              "silu_mul_fp8 requires R and I to be positive multiples of "
+              "16, got [", R, ", 2 * ", I, "]");
+  TORCH_CHECK(R <= INT32_MAX && gu.size(1) <= INT32_MAX,
+              "silu_mul_fp8: R and 2I must fit in int32");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0,
+              "silu_mul_fp8 requires a 16-byte aligned tensor");
+  fp8_check_scale(scale, gu);
+  auto opts = gu.options().dtype(at::kFloat8_e4m3fn);
+  auto q = torch::empty({R, I}, opts);
+  auto qt = torch::empty({I, R}, opts);
+  auto partials = fp8_new_partials(gu, R, I);
+  silu_mul_fp8_launch(gu.data_ptr(), scale.data_ptr<float>(), q.data_ptr(),
+                      qt.data_ptr(), partials.data_ptr(), (int)R, (int)I,
+                      cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {q, qt, partials};
+}
+
+// Fold the partials into this step's amax, put it into history[slot] in
+// place (slot < 0: into every slot) and return a fresh f32 [2] = {scale,
+// inv_scale} of max(history)
+torch::Tensor fp8_history_update(torch::Tensor partials,
+                                 torch::Tensor history, int64_t slot) {
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
+                  partials.dtype() == torch::kInt && partials.numel() > 0 &&
+                  partials.numel() <= INT32_MAX,
+              "partials must be a non-empty contiguous int32 GPU tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(partials.data_ptr()) % 16 == 0,
+              "partials must be 16-byte aligned");
+  TORCH_CHECK(history.is_cuda() && history.device() == partials.device() &&
+                  history.is_contiguous() &&
+                  history.dtype() == torch::kFloat && history.dim() == 1 &&
+                  history.numel() > 0 && history.numel() <= 1024,
+              "history must be a contiguous f32 [L] tensor, 1 <= L <= 1024, "
+              "on the partials' device");
+  TORCH_CHECK(slot < history.numel(), "slot ", slot,
+              " is outside the history of ", history.numel());
+  auto out = torch::empty({2}, history.options());
+  fp8_history_update_launch(partials.data_ptr(), (int)partials.numel(),
+                            history.data_ptr<float>(), (int)history.numel(),
+                            (int)(slot < 0 ? -1 : slot),
+                            out.data_ptr<float>(), cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return out;
+}
+
 // ---------------- attention ----------------
 // doc_start / doc_end are the [B,S] int32 tables of ops/doc_mask.py (their
 // contents are the caller's contract; the kernels only keep a bad table
@@ -1042,6 +1136,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_scale_", &grad_scale_);
   m.def("fp8_amax_scale", &fp8_amax_scale);
   m.def("fp8_cast_transpose", &fp8_cast_transpose);
+  m.def("fp8_cast_amax", &fp8_cast_amax);
+  m.def("silu_mul_fp8", &silu_mul_fp8);
+  m.def("fp8_history_update", &fp8_history_update);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_fwd_doc", &attn_fwd_doc);

@@ -50,22 +50,10 @@
 // the binding), so a lane's 4x16 patch and every 16 B run is entirely inside
 // or outside the tensor; tiles may hang over either edge.
 #include "common.h"
+#include "fp8_tile.h"
 #include "launchers.h"
 
-#define FP8_E4M3_MAX 448.0f
-#define FP8_AMAX_FLOOR 1e-12f
-#define FP8_TILE 64
-
 // ---------------------------------------------------------------- amax
-__device__ __forceinline__ uint32_t wave_reduce_umax(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)v, off, WAVE);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // 256 threads; the result is valid in thread 0
 __device__ __forceinline__ uint32_t block4_umax(uint32_t v, uint32_t* sh) {
   v = wave_reduce_umax(v);
@@ -119,90 +107,25 @@ __global__ void __launch_bounds__(256) fp8_scale_final_kernel(
 }
 
 // ---------------------------------------------------------------- cast
-__device__ __forceinline__ float fp8_scale_clamp(short bits, float scale) {
-  float v = bf2f(bits) * scale;
-  v = v > FP8_E4M3_MAX ? FP8_E4M3_MAX : v;
-  v = v < -FP8_E4M3_MAX ? -FP8_E4M3_MAX : v;
-  return v;
-}
-
-// four e4m3 in one dword, a in the lowest byte
-__device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c,
-                                               float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (uint32_t)w;
-}
-
 template <bool ROW, bool TR>
 __global__ void __launch_bounds__(64) fp8_cast_transpose_kernel(
     const short* __restrict__ x, const float* __restrict__ scale_p,
     uint8_t* __restrict__ q, uint8_t* __restrict__ qt, int R, int C,
     int tiles_c) {
-  // [col in tile][row in tile / 4] dwords of 4 e4m3 down the rows
   __shared__ __attribute__((aligned(16))) uint32_t image[FP8_TILE * 16];
-  const int lane = threadIdx.x;
-  const int cb = lane & 3;   // block of 16 columns
-  const int rg = lane >> 2;  // group of 4 rows
-  const int bid = (int)blockIdx.x;
-  const int tile_r = (bid / tiles_c) * FP8_TILE;
-  const int tile_c = (bid % tiles_c) * FP8_TILE;
-  const int r0 = tile_r + rg * 4;
-  const int c0 = tile_c + cb * 16;
-  const bool inside = r0 < R && c0 < C;
-
-  if (inside) {
+  const Fp8Tile t = fp8_tile(R, C, tiles_c);
+  if (t.inside) {
     const float scale = *scale_p;
     s16x8 raw[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const short* src = x + (int64_t)(r0 + i) * C + c0;
+      const short* src = x + (int64_t)(t.r0 + i) * C + t.c0;
       raw[i][0] = *reinterpret_cast<const s16x8*>(src);
       raw[i][1] = *reinterpret_cast<const s16x8*>(src + 8);
     }
-    float v[4][16];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        v[i][j] = fp8_scale_clamp(raw[i][0][j], scale);
-        v[i][8 + j] = fp8_scale_clamp(raw[i][1][j], scale);
-      }
-    if constexpr (ROW) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        u32x4 w;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-          w[m] = pack4_e4m3(v[i][4 * m], v[i][4 * m + 1], v[i][4 * m + 2],
-                            v[i][4 * m + 3]);
-        *reinterpret_cast<u32x4*>(q + (int64_t)(r0 + i) * C + c0) = w;
-      }
-    }
-    if constexpr (TR) {
-      const int d = rg ^ ((cb & 1) << 3);
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        image[(cb * 16 + k) * 16 + d] =
-            pack4_e4m3(v[0][k], v[1][k], v[2][k], v[3][k]);
-    }
+    fp8_patch_store<ROW, TR>(raw, scale, t, image, q, C);
   }
-  if constexpr (TR) {
-    __syncthreads();
-    const int run = lane & 3;  // 16 tile rows = one 16 B run of a qt row
-    const int gr = tile_r + run * 16;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int col = i * 16 + (lane >> 2);  // column block i
-      const int gc = tile_c + col;
-      if (gc < C && gr < R) {
-        const int slot = run ^ ((i & 1) << 1);
-        const u32x4 w =
-            *reinterpret_cast<const u32x4*>(&image[col * 16 + slot * 4]);
-        *reinterpret_cast<u32x4*>(qt + (int64_t)gc * R + gr) = w;
-      }
-    }
-  }
+  if constexpr (TR) fp8_image_flush(image, t, qt, R, C);
 }
 
 extern "C" {

@@ -187,6 +187,27 @@ void fp8_amax_scale_launch(const void* x, int64_t numel, void* partials,
 void fp8_cast_transpose_launch(const void* x, const float* scale, void* q,
                                void* qt, int R, int C, hipStream_t s);
 
+// fp8_delayed.hip: the one-pass forms for a scale known up front, same
+// tensor requirements.  fp8_cast_amax_launch is fp8_cast_transpose_launch
+// that also writes one sign-cleared bf16 bit pattern per 64x64 tile to
+// `partials` (fp8_tiles(R, C) dwords, no initialisation needed).
+// silu_mul_fp8_launch quantises h = silu(gate) * up of gu [R, 2I] (gate | up
+// packed, R % 16 == 0 and I % 16 == 0) without writing h: q [R, I], qt
+// [I, R], fp8_tiles(R, I) partials.  fp8_history_update_launch folds nparts
+// >= 1 partials (16 B aligned) into this step's amax, writes it to
+// history[slot] (f32 [L], L >= 1; slot < 0 fills every slot; a non-finite
+// amax is replaced by the previous max(history)) and out[0] = 448 /
+// max(max(history), 1e-12), out[1] = its reciprocal quotient.
+int64_t fp8_tiles(int R, int C);
+void fp8_cast_amax_launch(const void* x, const float* scale, void* q,
+                          void* qt, void* partials, int R, int C,
+                          hipStream_t s);
+void silu_mul_fp8_launch(const void* gu, const float* scale, void* q, void* qt,
+                         void* partials, int R, int I, hipStream_t s);
+void fp8_history_update_launch(const void* partials, int nparts,
+                               float* history, int L, int slot, float* out,
+                               hipStream_t s);
+
 // attention_fwd.hip, attention_bwd.hip.  doc_start / doc_end are the [B,S]
 // int32 tables of the document-masked mode for packed rows (first token /
 // exclusive end of each token's document); null selects the plain causal

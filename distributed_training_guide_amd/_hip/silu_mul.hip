@@ -11,6 +11,7 @@
 //   silu(x) = x * sigmoid(x);  d/dx silu = sigmoid(x) * (1 + x * (1 - sigmoid(x)))
 #include "common.h"
 #include "launchers.h"
+#include "silu.h"
 
 __global__ void __launch_bounds__(256) silu_mul_fwd_kernel(
     const short* __restrict__ gu, short* __restrict__ y, int64_t nrows,
@@ -27,11 +28,8 @@ __global__ void __launch_bounds__(256) silu_mul_fwd_kernel(
       s16x8 uv = *reinterpret_cast<const s16x8*>(u + i);
       s16x8 o;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = bf2f(gv[j]);
-        float sig = 1.0f / (1.0f + __expf(-x));
-        o[j] = f2bf(x * sig * bf2f(uv[j]));
-      }
+      for (int j = 0; j < 8; ++j)
+        o[j] = f2bf(silu_mul_f32(bf2f(gv[j]), bf2f(uv[j])));
       *reinterpret_cast<s16x8*>(yr + i) = o;
     }
   }

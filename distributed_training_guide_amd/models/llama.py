@@ -23,6 +23,7 @@ import torch.nn as nn
 from ..ops import (RMSNorm, causal_lm_loss, doc_bounds, flash_attention,
                    moe_mlp, qkv_norm_rope, qkv_rope, silu_mul)
 from ..ops.embedding import Embedding
+from ..ops.fp8_linear import fp8_swiglu_linear
 from ..ops.fused_linear_ce import fused_causal_lm_loss
 from ..ops.rmsnorm import add_rmsnorm
 
@@ -158,6 +159,12 @@ class LlamaMLP(nn.Module):
                                    dtype=dtype)
 
     def forward(self, x):
+        # a down projection under FP8 delayed scaling takes SwiGLU's result
+        # as e4m3 straight from the kernel (ops/fp8_linear.py)
+        state = getattr(self.down_proj, "fp8_state", None)
+        if state is not None:
+            return fp8_swiglu_linear(self.gate_up_proj(x),
+                                     self.down_proj.weight, state)
         return self.down_proj(silu_mul(self.gate_up_proj(x)))
 
 

@@ -12,7 +12,8 @@ Extras the reference ships as diff-recipes are first-class flags:
 --grad-accum-steps (related-topics/gradient-accumulation, incl. no_sync),
 --deterministic + RNG checkpointing (related-topics/determinism),
 --wandb (wandb-configurations topologies),
---fp8 (FP8 projection GEMMs, ops/fp8_linear.py; Llama, single and DDP),
+--fp8 (FP8 projection GEMMs, ops/fp8_linear.py; Llama, single and DDP;
+--fp8-recipe delayed scales by an amax history of --fp8-amax-history),
 --router-aux-loss-coef / --router-z-loss-coef (mixture-of-experts router
 losses, ops/moe.py).
 """
@@ -77,6 +78,16 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
                        help="run the qkv/o/gate_up/down projection GEMMs in "
                             "FP8 (e4m3, tensor-wise dynamic scaling); Llama "
                             "models, single-device and DDP strategies only")
+        p.add_argument("--fp8-recipe", default="dynamic",
+                       choices=["dynamic", "delayed"],
+                       help="with --fp8: `dynamic` scales every tensor by "
+                            "its own amax (two passes); `delayed` by the "
+                            "amaxes of its last --fp8-amax-history "
+                            "quantisations (one pass, and SwiGLU writes "
+                            "e4m3 directly)")
+        p.add_argument("--fp8-amax-history", default=16, type=int,
+                       help="with --fp8-recipe delayed: amaxes kept per "
+                            "operand of each linear")
         p.add_argument("--router-aux-loss-coef", default=0.0, type=float,
                        help="mixture-of-experts models: weight of the "
                             "router's load-balancing loss, averaged over "
@@ -141,18 +152,20 @@ def apply_router_loss_coefs(config, args):
     return dataclasses.replace(config, **coefs)
 
 
-def apply_fp8(model):
+def apply_fp8(model, recipe="dynamic", history=16):
     """Convert the Llama projections (qkv_proj, o_proj, gate_up_proj,
     down_proj) to FP8 linears in place; lm_head and embeddings stay bf16,
     and so does a mixture-of-experts layer (its router is skipped by name,
     its experts are 3-D parameters, not linears)."""
     from .ops import convert_linears_to_fp8
 
-    names = convert_linears_to_fp8(model, skip=("lm_head", "router"))
+    names = convert_linears_to_fp8(model, skip=("lm_head", "router"),
+                                   recipe=recipe, history=history)
     if not names:
         raise ValueError("--fp8: the model has no bias-free linear with "
                          "dimensions that are multiples of 16 to convert")
-    LOGGER.info(f"FP8 (e4m3) GEMMs in {len(names)} linears")
+    LOGGER.info(f"FP8 (e4m3) GEMMs in {len(names)} linears, {recipe} "
+                "scaling")
     return names
 
 
@@ -191,7 +204,8 @@ def run_training(args, strategy):
         check_fp8_supported(config, strategy)
     model, optimizer, lr_scheduler = strategy.build(config, args)
     if getattr(args, "fp8", False):
-        apply_fp8(model)
+        apply_fp8(model, getattr(args, "fp8_recipe", "dynamic"),
+                  getattr(args, "fp8_amax_history", 16))
     if getattr(args, "master_weights", False):
         log_master_weights(optimizer)
     n_local = sum(p.numel() for p in model.parameters())

@@ -19,6 +19,16 @@ process, alternating, in this one run.  The figure is the trainer's own
 time/total (phase timers fenced by device synchronisation) over the log
 windows after the first.
 
+--recipe delayed compares delayed scaling (fp8_delayed.hip) with the dynamic
+recipe instead: per operand the one-pass cast+amax with its history update
+against amax + cast (4 B against 6 B per element with both outputs, 3 B
+against 5 B with one), the fold/update launch alone, SwiGLU written as e4m3
+against silu_mul + amax + cast (6 B against 12 B per element of h), forward
+plus backward per layer and of the whole MLP with and without the fused
+SwiGLU, and with --e2e the trainer under both recipes (--loss-steps N also
+records the loss of the first N steps side by side).  Writes
+profiles/fp8_delayed.json.
+
 Numbers are reported, not gated.  Writes profiles/fp8_linear.json.
 """
 import argparse
@@ -147,11 +157,161 @@ def run_trainer(fp8, model, steps, log_freq, batch, seq, timeout,
                 i["tokens_per_s"] for i in steady), 1),
             "windows_ms": [round(i["time/total"], 2) for i in steady],
             "loss_last_window": round(infos[-1]["running_loss"], 4),
+            "loss_windows": [round(i["running_loss"], 4) for i in infos],
             "peak_alloc_gb": infos[-1].get("peak_alloc_gb")}
+
+
+def alternate(variants, warmup, repeats):
+    """{name: {ms, min_ms, max_ms}}, the variants alternating in one run."""
+    ts = {k: [] for k in variants}
+    for it in range(warmup + repeats):
+        for key, fn in variants.items():
+            t = timed(fn, 0, 1)
+            if it >= warmup:
+                ts[key] += t
+    return {k: {"ms": round(statistics.median(v), 4),
+                "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+            for k, v in ts.items()}
+
+
+def bench_delayed_layer(name, M, N, K, warmup, repeats):
+    from distributed_training_guide_amd._ext import ext
+    from distributed_training_guide_amd.ops import (Fp8DelayedState,
+                                                    fp8_linear, fp8_quantize)
+
+    dev = torch.device("cuda")
+    x = torch.randn(M, K, device=dev).bfloat16().requires_grad_()
+    w = (0.02 * torch.randn(N, K, device=dev)).bfloat16().requires_grad_()
+    dy = torch.randn(M, N, device=dev).bfloat16()
+    state = Fp8DelayedState()
+
+    def run(st):
+        x.grad = w.grad = None
+        fp8_linear(x, w, st).backward(dy)
+
+    run(state)  # seed the three roles
+    row = {"M": M, "N": N, "K": K,
+           "fwd_bwd": alternate({"dynamic": lambda: run(None),
+                                 "delayed": lambda: run(state)},
+                                warmup, repeats)}
+    operands = {"x": (x.detach(), True, True, 6, 4),
+                "w": (w.detach(), True, False, 5, 3),
+                "dy": (dy, True, True, 6, 4)}
+    row["quant"] = {}
+    for role, (t, rw, tr, b_dyn, b_del) in operands.items():
+        r = alternate({"dynamic": lambda: fp8_quantize(t, rw, tr),
+                       "delayed": lambda: state.quantize(t, role, rw, tr)},
+                      warmup, repeats)
+        for key, b in (("dynamic", b_dyn), ("delayed", b_del)):
+            r[key]["floor_bytes"] = t.numel() * b
+            r[key]["tb_per_s"] = round(
+                t.numel() * b / (r[key]["ms"] * 1e-3) / 1e12, 2)
+        row["quant"][role] = r
+    # the fold + history update launch of the largest operand, alone
+    big = max((x.detach(), dy), key=lambda t: t.numel())
+    _, _, partials = ext().fp8_cast_amax(big, state.role("x").pair[0], True,
+                                         True)
+    hist = torch.zeros(16, device=dev)
+    row["history_update"] = dict(
+        alternate({"k": lambda: ext().fp8_history_update(partials, hist, 0)},
+                  warmup, repeats)["k"], partials=partials.numel())
+    print(name, json.dumps(row), flush=True)
+    return row
+
+
+def bench_delayed_mlp(M, warmup, repeats):
+    from distributed_training_guide_amd.ops import (Fp8DelayedState,
+                                                    fp8_linear, fp8_quantize,
+                                                    fp8_swiglu_linear,
+                                                    silu_mul)
+
+    dev = torch.device("cuda")
+    H, I = PROJECTIONS["down_proj"]
+    gu = torch.randn(M, 2 * I, device=dev).bfloat16()
+    st = Fp8DelayedState()
+    st.swiglu(gu)  # seed
+    res = {"rows": M, "I": I, "floor_bytes": {"unfused": M * I * 12,
+                                              "fused": M * I * 6}}
+    res["swiglu_quant"] = alternate(
+        {"unfused": lambda: fp8_quantize(silu_mul(gu), True, True),
+         "fused": lambda: st.swiglu(gu)}, warmup, repeats)
+    for key in ("unfused", "fused"):
+        r = res["swiglu_quant"][key]
+        r["tb_per_s"] = round(res["floor_bytes"][key] / (r["ms"] * 1e-3)
+                              / 1e12, 2)
+    del gu
+    x = torch.randn(M, H, device=dev).bfloat16().requires_grad_()
+    wgu = (0.02 * torch.randn(2 * I, H, device=dev)).bfloat16() \
+        .requires_grad_()
+    wd = (0.02 * torch.randn(H, I, device=dev)).bfloat16().requires_grad_()
+    dy = torch.randn(M, H, device=dev).bfloat16()
+    s1, s2, s3, s4 = (Fp8DelayedState() for _ in range(4))
+    mlps = {
+        "dynamic": lambda: fp8_linear(silu_mul(fp8_linear(x, wgu)), wd),
+        "delayed": lambda: fp8_linear(
+            silu_mul(fp8_linear(x, wgu, s1)), wd, s2),
+        "delayed_fused_swiglu": lambda: fp8_swiglu_linear(
+            fp8_linear(x, wgu, s3), wd, s4),
+    }
+
+    def run(f):
+        x.grad = wgu.grad = wd.grad = None
+        f().backward(dy)
+
+    for f in mlps.values():
+        run(f)  # seed
+    res["mlp_fwd_bwd"] = alternate(
+        {k: (lambda f=f: run(f)) for k, f in mlps.items()}, warmup, repeats)
+    print("mlp", json.dumps(res), flush=True)
+    return res
+
+
+def main_delayed(args, result):
+    if not args.skip_layers:
+        result["layers"] = {
+            name: bench_delayed_layer(name, args.rows, N, K, args.warmup,
+                                      args.repeats)
+            for name, (N, K) in PROJECTIONS.items()}
+        torch.cuda.empty_cache()
+        result["mlp"] = bench_delayed_mlp(args.rows, args.warmup,
+                                          args.repeats)
+        torch.cuda.empty_cache()
+    recipes = {"dynamic": (), "delayed": ("--fp8-recipe", "delayed")}
+    if args.e2e:
+        runs = []
+        for pair in range(args.e2e_pairs):
+            for key, extra in recipes.items():  # alternate
+                r = run_trainer(True, args.e2e_model, args.e2e_steps,
+                                args.e2e_log_freq, args.e2e_batch,
+                                args.e2e_seq, args.e2e_timeout, extra)
+                r["recipe"] = key
+                runs.append(r)
+                print("e2e", json.dumps(r), flush=True)
+        result["e2e"] = {"model": args.e2e_model, "batch": args.e2e_batch,
+                         "seq": args.e2e_seq, "runs": runs}
+        for key in recipes:
+            result["e2e"][f"{key}_ms_per_step"] = round(statistics.mean(
+                r["ms_per_step"] for r in runs if r["recipe"] == key), 2)
+    if args.loss_steps:
+        result["loss"] = {"steps": args.loss_steps, "window": 10}
+        for key, extra in recipes.items():
+            r = run_trainer(True, args.e2e_model, args.loss_steps, 10,
+                            args.e2e_batch, args.e2e_seq, args.e2e_timeout,
+                            extra)
+            result["loss"][key] = r["loss_windows"]
+            print("loss", key, json.dumps(r["loss_windows"]), flush=True)
 
 
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--recipe", default="dynamic",
+                   choices=["dynamic", "delayed"],
+                   help="dynamic: fp8 against bf16 (profiles/fp8_linear."
+                        "json); delayed: delayed against dynamic scaling "
+                        "(profiles/fp8_delayed.json)")
+    p.add_argument("--loss-steps", type=int, default=0,
+                   help="--recipe delayed: also record the loss of the "
+                        "first N trainer steps under both recipes")
     p.add_argument("--rows", type=int, default=24576, help="M of every GEMM")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--repeats", type=int, default=10)
@@ -166,8 +326,11 @@ def main():
     p.add_argument("--e2e-timeout", type=int, default=420,
                    help="seconds allowed to one trainer process")
     p.add_argument("--skip-layers", action="store_true")
-    p.add_argument("--out", default="profiles/fp8_linear.json")
+    p.add_argument("--out", default=None)
     args = p.parse_args()
+    if args.out is None:
+        args.out = ("profiles/fp8_linear.json" if args.recipe == "dynamic"
+                    else "profiles/fp8_delayed.json")
 
     if not torch.cuda.is_available():
         sys.exit("bench_fp8_linear needs a GPU: timings are not measured "
@@ -179,6 +342,12 @@ def main():
     result = {"device": torch.cuda.get_device_name(0),
               "torch": torch.__version__, "rows": args.rows,
               "warmup": args.warmup, "repeats": args.repeats}
+    if args.recipe == "delayed":
+        main_delayed(args, result)
+        out = Path(args.out)
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps(result, indent=2) + "\n")
+        return
     if not args.skip_layers:
         layers = {name: bench_layer(name, args.rows, N, K, args.warmup,
                                     args.repeats)
