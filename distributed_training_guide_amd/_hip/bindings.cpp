@@ -657,6 +657,31 @@ torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor ids, int64_t V) {
   return dtable;
 }
 
+// the atomic-free form: its scratch is O(N) + O(V) ints and N / 128 f32 rows
+torch::Tensor embedding_bwd_sorted(torch::Tensor dy, torch::Tensor ids,
+                                   int64_t V) {
+  CHECK_BF16_CONTIG(dy);
+  TORCH_CHECK(ids.is_cuda() && ids.device() == dy.device(),
+              "ids must be on dy's device");
+  TORCH_CHECK(ids.dtype() == torch::kLong && ids.is_contiguous());
+  TORCH_CHECK(dy.dim() >= 1 && V > 0, "dy must be [..., H] and V positive");
+  const int H = (int)dy.size(-1);
+  TORCH_CHECK(dy.numel() == ids.numel() * H, "dy/ids shape mismatch");
+  const int64_t N = ids.numel();
+  TORCH_CHECK(N < INT32_MAX - 1024 && V <= ((int64_t)1 << 30),
+              "embedding_bwd_sorted: ids.numel() and V must fit an int32");
+  auto scratch = torch::empty({embed_bwd_sorted_scratch(N, V)},
+                              dy.options().dtype(torch::kInt));
+  auto partials = torch::empty({embed_bwd_sorted_partials(N), (int64_t)H},
+                               dy.options().dtype(torch::kFloat));
+  auto dtable = torch::empty({V, (int64_t)H}, dy.options());
+  embed_bwd_sorted_launch(dy.data_ptr(), ids.data_ptr<int64_t>(),
+                          scratch.data_ptr<int>(), partials.data_ptr<float>(),
+                          dtable.data_ptr(), N, H, V, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dtable;
+}
+
 // ---------------- gelu (GPT-2 MLP) ----------------
 torch::Tensor gelu_fwd(torch::Tensor x) {
   CHECK_BF16_CONTIG(x);
@@ -1119,6 +1144,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul_bwd", &silu_mul_bwd);
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
+  m.def("embedding_bwd_sorted", &embedding_bwd_sorted);
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);
   m.def("gelu_fwd", &gelu_fwd);

@@ -138,6 +138,18 @@ void embed_bwd_launch(const void* dy, const int64_t* ids, float* acc,
                       void* dtable, int64_t nrows, int H, int64_t V,
                       hipStream_t s);
 
+// embedding_bwd_sorted.hip: the same gradient without atomics, in an order
+// fixed by ids (stable sort of the positions by id, then one wave per table
+// row, long rows cut into pieces summed in parallel).  `scratch` is embed_bwd_sorted_scratch(N, V) int32 and `partials`
+// embed_bwd_sorted_partials(N) rows of [H] f32 (null where that is 0);
+// neither needs initialisation.  N = nrows < 2^31 - 1024 (N == 0 writes
+// zeros), V <= 2^30; every row of dtable is written.
+int64_t embed_bwd_sorted_scratch(int64_t N, int64_t V);
+int64_t embed_bwd_sorted_partials(int64_t N);
+void embed_bwd_sorted_launch(const void* dy, const int64_t* ids, int* scratch,
+                             float* partials, void* dtable, int64_t N, int H,
+                             int64_t V, hipStream_t s);
+
 // cross_entropy.hip
 void ce_fwd_launch(const void* logits, const int64_t* labels, float* loss,
                    float* lse, int64_t nrows, int S_logits, int S_out, int V,
