@@ -592,6 +592,70 @@ std::vector<torch::Tensor> moe_combine_bwd(torch::Tensor dy,
   return {dyp, dw};
 }
 
+// ---------------- expert GEMMs (moe_gemm.hip) ----------------
+// rows bf16 [N, inner], weight bf16 [E, M, K], offs int32 [E]: the contract
+// of ops/moe.py's moe_gemm_supported, checked again here
+inline void moe_gemm_check(const torch::Tensor& rows, int64_t E, int64_t M,
+                           int64_t K, const torch::Tensor& offs,
+                           const char* what) {
+  CHECK_BF16_CONTIG(rows);
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) <= INT32_MAX - 256, what,
+              ": rows must be [N, .] with N < 2^31 - 256");
+  TORCH_CHECK(E >= 1 && E <= 128, what, ": E must be in [1, 128], got ", E);
+  TORCH_CHECK(M >= 64 && M % 64 == 0 && K >= 64 && K % 64 == 0 &&
+                  E * M * K <= INT64_MAX / 4 && M <= (1 << 24) &&
+                  K <= (1 << 24),
+              what, ": M and K must be positive multiples of 64, got ", M,
+              ", ", K);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0, what,
+              ": rows must be 16-byte aligned");
+  CHECK_ON_DEVICE_CONTIG(offs, rows, torch::kInt, "int32");
+  TORCH_CHECK(offs.dim() == 1 && offs.size(0) == E, what,
+              ": offs must be [E]");
+}
+
+// trans_b false: y [N, M] = a [N, K] . weight[e]^T; true: da [N, K] =
+// a (= dy) [N, M] . weight[e], per expert group of rows
+torch::Tensor moe_gemm_rows(torch::Tensor a, torch::Tensor weight,
+                            torch::Tensor offs, bool trans_b) {
+  TORCH_CHECK(weight.dim() == 3, "moe_gemm_rows: weight must be [E, M, K]");
+  const int64_t E = weight.size(0), M = weight.size(1), K = weight.size(2);
+  moe_gemm_check(a, E, M, K, offs, "moe_gemm_rows");
+  CHECK_ON_DEVICE_CONTIG(weight, a, torch::kBFloat16, "bf16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0,
+              "moe_gemm_rows: weight must be 16-byte aligned");
+  TORCH_CHECK(a.size(1) == (trans_b ? M : K),
+              "moe_gemm_rows: rows' width must be weight's ",
+              trans_b ? "M" : "K");
+  const int64_t N = a.size(0);
+  TORCH_CHECK((N / 128 + 1 + E) * ((M > K ? M : K) / 128 + 1) <= INT32_MAX,
+              "moe_gemm_rows: too many tiles for one grid");
+  auto out = torch::empty({N, trans_b ? K : M}, a.options());
+  moe_gemm_rows_launch(a.data_ptr(), weight.data_ptr(), offs.data_ptr<int>(),
+                       out.data_ptr(), N, (int)E, (int)M, (int)K,
+                       trans_b ? 1 : 0, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return out;
+}
+
+// dw [E, M, K] = dy[rows of e]^T . a[rows of e]
+torch::Tensor moe_gemm_dw(torch::Tensor dy, torch::Tensor a,
+                          torch::Tensor offs) {
+  TORCH_CHECK(dy.dim() == 2 && a.dim() == 2 && dy.size(0) == a.size(0),
+              "moe_gemm_dw: dy [N, M] and a [N, K]");
+  const int64_t E = offs.numel(), M = dy.size(1), K = a.size(1);
+  moe_gemm_check(dy, E, M, K, offs, "moe_gemm_dw");
+  moe_gemm_check(a, E, M, K, offs, "moe_gemm_dw");
+  TORCH_CHECK(E * (M / 128 + 1) * (K / 128 + 1) <= INT32_MAX,
+              "moe_gemm_dw: too many tiles for one grid");
+  auto dw = torch::empty({E, M, K}, a.options());
+  moe_gemm_dw_launch(dy.data_ptr(), a.data_ptr(), offs.data_ptr<int>(),
+                     dw.data_ptr(), a.size(0), (int)E, (int)M, (int)K,
+                     cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dw;
+}
+
 // ---------------- silu_mul ----------------
 torch::Tensor silu_mul_fwd(torch::Tensor gu) {
   CHECK_BF16_CONTIG(gu);
@@ -1140,6 +1204,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_scatter", &moe_scatter);
   m.def("moe_combine", &moe_combine);
   m.def("moe_combine_bwd", &moe_combine_bwd);
+  m.def("moe_gemm_rows", &moe_gemm_rows);
+  m.def("moe_gemm_dw", &moe_gemm_dw);
   m.def("silu_mul_fwd", &silu_mul_fwd);
   m.def("silu_mul_bwd", &silu_mul_bwd);
   m.def("embedding_fwd", &embedding_fwd);

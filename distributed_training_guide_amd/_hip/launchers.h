@@ -131,6 +131,22 @@ void moe_scatter_launch(const void* x, const int* dest, const float* w,
 void moe_combine_launch(const void* yp, const int* dest, const float* w,
                         void* y, int64_t T, int H, int k, hipStream_t s);
 
+// moe_gemm.hip: the expert GEMMs over the expert-sorted rows.  a [N, K],
+// weight [E, M, K], dy / y [N, M], all bf16, 16 B aligned, M and K multiples
+// of 64, E <= 128; offs int32 [E] as moe_index_launch writes it, read on the
+// device only (values outside [0, N] are clamped).
+// moe_gemm_rows_launch: trans_b == 0 writes out [N, M] = rows . weight[e]^T
+// from rows = a; trans_b != 0 writes out [N, K] = rows . weight[e] from
+// rows = dy [N, M].  Rows that offs assigns to no expert are not written.
+// moe_gemm_dw_launch: dw [E, M, K] = dy[rows of e]^T . a[rows of e], every
+// element written once, zeros for an expert without rows.
+void moe_gemm_rows_launch(const void* rows, const void* weight,
+                          const int* offs, void* out, int64_t N, int E, int M,
+                          int K, int trans_b, hipStream_t s);
+void moe_gemm_dw_launch(const void* dy, const void* a, const int* offs,
+                        void* dw, int64_t N, int E, int M, int K,
+                        hipStream_t s);
+
 // embedding.hip
 void embed_fwd_launch(const void* table, const int64_t* ids, void* out,
                       int64_t nrows, int H, int64_t V, hipStream_t s);

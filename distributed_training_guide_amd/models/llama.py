@@ -66,6 +66,9 @@ class LlamaConfig:
     # of the router z-loss.  With both 0 the router is called without them.
     router_aux_loss_coef: float = 0.0
     router_z_loss_coef: float = 0.0
+    # the expert GEMMs (ops/moe.py expert_mm): "torch" is torch's grouped
+    # GEMM, "hip" the hand-written grouped GEMMs of _hip/moe_gemm.hip
+    expert_gemm: str = "torch"
 
     @property
     def router_losses(self) -> bool:
@@ -185,6 +188,7 @@ class LlamaMoE(nn.Module):
                 f"{config.num_experts_per_tok}")
         self.top_k = config.num_experts_per_tok
         self.norm_topk_prob = config.norm_topk_prob
+        self.expert_gemm = config.expert_gemm
         # (aux, z) of the latest forward.  One attribute, overwritten every
         # forward: the model reads it right after the layer loop, so the
         # loss is built on the graph of that forward, and a checkpoint
@@ -202,10 +206,12 @@ class LlamaMoE(nn.Module):
         if self.router_losses:
             y, *self.aux_losses = moe_mlp(
                 tokens, self.router.weight, self.gate_up_proj,
-                self.down_proj, self.top_k, self.norm_topk_prob, aux=True)
+                self.down_proj, self.top_k, self.norm_topk_prob, aux=True,
+                expert_gemm=self.expert_gemm)
         else:
             y = moe_mlp(tokens, self.router.weight, self.gate_up_proj,
-                        self.down_proj, self.top_k, self.norm_topk_prob)
+                        self.down_proj, self.top_k, self.norm_topk_prob,
+                        expert_gemm=self.expert_gemm)
         return y.view(x.shape)
 
 

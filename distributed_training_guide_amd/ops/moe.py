@@ -8,7 +8,10 @@ torch's grouped GEMM with device-side group offsets), and the memory-bound
 work around them is hand-written HIP: softmax -> top-k -> renormalise, the
 expert-sorted layout, the row scatter into it and the k-way weighted combine
 back, each with its backward.  No host sync, no atomics (so no
-non-deterministic index_add_), no cleared buffers.
+non-deterministic index_add_), no cleared buffers.  The expert GEMMs have a
+hand-written alternative as well, opt-in: expert_mm(impl="hip") /
+moe_mlp(expert_gemm="hip") run the grouped bf16 MFMA GEMMs of moe_gemm.hip,
+forward and backward.
 
 Layout.  Slot s = t*k + j is token t's j-th selected expert.  `dest[s]` is
 the slot's row in the expert-sorted layout (rows of one expert contiguous,
@@ -245,10 +248,13 @@ def moe_combine(yp, dest, w):
 # --------------------------------------------------------------------------
 # expert GEMMs and the composed layer
 # --------------------------------------------------------------------------
-# "grouped" or "loop": which path the last expert_mm call took (reporting
-# only; the decision is kept per device type in _grouped_mm_works)
+# "grouped", "loop" or "hip": which path the last expert_mm call took
+# (reporting only; the torch decision is kept per device type in
+# _grouped_mm_works)
 last_expert_mm_path = None
 _grouped_mm_works = {}  # device type -> bool, decided by the first call
+EXPERT_GEMM_IMPLS = ("torch", "hip")
+MOE_GEMM_MAX_EXPERTS = 128
 
 
 def _expert_mm_loop(a, weight, offs):
@@ -259,10 +265,45 @@ def _expert_mm_loop(a, weight, offs):
     return torch.cat(parts)
 
 
-def expert_mm(a, weight, offs):
+class _ExpertMMFn(torch.autograd.Function):
+    """The three grouped GEMMs of moe_gemm.hip: y = a . w[e]^T forward,
+    da = dy . w[e] and dw[e] = dy[rows e]^T . a[rows e] backward.  offs stays
+    on the device throughout."""
+
+    @staticmethod
+    def forward(ctx, a, weight, offs):
+        ctx.save_for_backward(a, weight, offs)
+        return ext().moe_gemm_rows(a, weight, offs, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, weight, offs = ctx.saved_tensors
+        dy = dy.contiguous()
+        da = ext().moe_gemm_rows(dy, weight, offs, True) \
+            if ctx.needs_input_grad[0] else None
+        dw = ext().moe_gemm_dw(dy, a, offs) \
+            if ctx.needs_input_grad[1] else None
+        return da, dw, None
+
+
+def moe_gemm_supported(a, weight):
+    """What moe_gemm.hip serves: bf16 on the GPU, E <= 128, M and K
+    multiples of 64 (any N, any rows per expert)."""
+    E, M, K = weight.shape
+    return use_hip(a) and a.dtype == weight.dtype == torch.bfloat16 \
+        and weight.device == a.device and 1 <= E <= MOE_GEMM_MAX_EXPERTS \
+        and M >= 64 and M % 64 == 0 and K >= 64 and K % 64 == 0
+
+
+def expert_mm(a, weight, offs, impl="torch"):
     """Rows [offs[e-1], offs[e]) of a [N, K] times weight[e].T, for weight
     [E, M, K]: the one helper both expert GEMMs go through.  torch's grouped
     GEMM takes the device-side offsets, so nothing waits on the host.
+
+    impl="hip" takes the hand-written grouped GEMMs of moe_gemm.hip, forward
+    and backward, where moe_gemm_supported holds (no host read of offs, no
+    dependence on torch's grouped GEMM); on a CPU tensor or another shape or
+    dtype it is the torch path below, unchanged.
 
     Where this build of torch cannot run the grouped GEMM on a's kind of
     device, the helper warns once and from then on loops over the experts'
@@ -271,12 +312,18 @@ def expert_mm(a, weight, offs):
     refusal decides: the arguments are checked here first, so a caller's
     shape error is a ValueError, and running out of memory is re-raised."""
     global last_expert_mm_path
+    if impl not in EXPERT_GEMM_IMPLS:
+        raise ValueError(
+            f"expert_mm: impl must be one of {EXPERT_GEMM_IMPLS}, got {impl!r}")
     if a.dim() != 2 or weight.dim() != 3 or a.shape[1] != weight.shape[2] \
             or offs.shape != (weight.shape[0],) or offs.dtype != torch.int32:
         raise ValueError(
             f"expert_mm: a [N, K], weight [E, M, K], offs int32 [E]; got "
             f"{tuple(a.shape)}, {tuple(weight.shape)}, {tuple(offs.shape)} "
             f"{offs.dtype}")
+    if impl == "hip" and moe_gemm_supported(a, weight):
+        last_expert_mm_path = "hip"
+        return _ExpertMMFn.apply(a.contiguous(), weight.contiguous(), offs)
     kind = a.device.type
     if _grouped_mm_works.get(kind, True):
         try:
@@ -299,7 +346,7 @@ def expert_mm(a, weight, offs):
 
 
 def _mlp_chain(x, router_weight, gate_up, down, k, norm, aux, router, index,
-               scatter, combine):
+               scatter, combine, expert_gemm="torch"):
     E = gate_up.shape[0]
     logits = F.linear(x, router_weight)
     # without aux the router is called exactly as before the option existed
@@ -307,8 +354,8 @@ def _mlp_chain(x, router_weight, gate_up, down, k, norm, aux, router, index,
         else router(logits, k, norm)
     dest, offs = index(idx, E)
     xp = scatter(x, dest, k)
-    h = silu_mul(expert_mm(xp, gate_up, offs))
-    y = combine(expert_mm(h, down, offs), dest, w)
+    h = silu_mul(expert_mm(xp, gate_up, offs, expert_gemm))
+    y = combine(expert_mm(h, down, offs, expert_gemm), dest, w)
     return (y, *losses) if aux else y
 
 
@@ -323,17 +370,21 @@ def moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob=True,
 
 
 def moe_mlp(x, router_weight, gate_up, down, k, norm_topk_prob=True,
-            aux=False):
+            aux=False, expert_gemm="torch"):
     """A mixture-of-experts SwiGLU feed-forward over tokens x [T, H].
 
     router_weight [E, H]; gate_up [E, 2I, H] (gate | up packed, so silu_mul
     serves the activation on the sorted rows); down [E, H, I].  Every token
     goes through its k routed experts and the outputs are summed with the
     router's weights.  With `aux` it returns (y, aux, z), the router's two
-    auxiliary losses over these tokens (moe_router)."""
+    auxiliary losses over these tokens (moe_router).  `expert_gemm` is
+    expert_mm's `impl` for both expert GEMMs."""
+    if expert_gemm not in EXPERT_GEMM_IMPLS:
+        raise ValueError(f"moe_mlp: expert_gemm must be one of "
+                         f"{EXPERT_GEMM_IMPLS}, got {expert_gemm!r}")
     if use_hip(x):
         return _mlp_chain(x, router_weight, gate_up, down, k, norm_topk_prob,
                           aux, moe_router, moe_dispatch_index, moe_scatter,
-                          moe_combine)
+                          moe_combine, expert_gemm)
     return moe_mlp_eager(x, router_weight, gate_up, down, k, norm_topk_prob,
                          aux)

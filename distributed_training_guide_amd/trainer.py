@@ -15,7 +15,7 @@ Extras the reference ships as diff-recipes are first-class flags:
 --fp8 (FP8 projection GEMMs, ops/fp8_linear.py; Llama, single and DDP;
 --fp8-recipe delayed scales by an amax history of --fp8-amax-history),
 --router-aux-loss-coef / --router-z-loss-coef (mixture-of-experts router
-losses, ops/moe.py).
+losses, ops/moe.py), --expert-gemm (hand-written grouped expert GEMMs).
 """
 import argparse
 import dataclasses
@@ -95,6 +95,11 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
         p.add_argument("--router-z-loss-coef", default=0.0, type=float,
                        help="mixture-of-experts models: weight of the "
                             "router z-loss, averaged over the layers")
+        p.add_argument("--expert-gemm", default="torch",
+                       choices=["torch", "hip"],
+                       help="mixture-of-experts models: the expert GEMMs as "
+                            "torch's grouped GEMM or as the hand-written "
+                            "grouped GEMMs (_hip/moe_gemm.hip)")
         p.add_argument("--deterministic", action="store_true")
         p.add_argument("--wandb", action="store_true")
         p.add_argument("--wandb-mode", default="rank0",
@@ -200,6 +205,12 @@ def run_training(args, strategy):
         torch.use_deterministic_algorithms(True)
 
     config = apply_router_loss_coefs(get_config(args.model_name), args)
+    if getattr(args, "expert_gemm", "torch") != "torch":
+        if getattr(config, "num_experts", 0) < 1:
+            raise ValueError(
+                "--expert-gemm needs a mixture-of-experts model: "
+                f"{args.model_name} is dense and has no expert GEMMs")
+        config = dataclasses.replace(config, expert_gemm=args.expert_gemm)
     if getattr(args, "fp8", False):
         check_fp8_supported(config, strategy)
     model, optimizer, lr_scheduler = strategy.build(config, args)

@@ -33,6 +33,12 @@ router fwd / bwd of this build, the aux fwd (with its finishing launch) / bwd,
 and the torch-op chain for the same two losses from the logits and the
 selection (logsumexp, exp, bincount, two means) with autograd's backward.
 
+--expert-gemm times the expert GEMMs instead (default --out
+profiles/moe_gemm.json), alternating in one run: forward, dA and dW of the
+gate_up and the down GEMM as torch's grouped GEMM and as moe_gemm.hip, with
+the achieved TFLOP/s from the shapes (2 N M K per product), and the whole
+layer forward + backward with either.
+
 --e2e-layers L additionally times training steps of a cut-down model of the
 same layer shape with L layers (the 30B model's 366 GB of parameter and
 optimizer state do not fit one GPU).  Results go to --out; no threshold is
@@ -116,6 +122,75 @@ def e2e(args, dev):
             "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1)}
 
 
+def expert_gemm_mode(args, C, moe, silu_mul, x, router_w, gate_up, down, xp,
+                     offs, dy, fwd, bwd):
+    """The six products of the two expert GEMMs (forward, dA, dW of gate_up
+    [E, 2I, H] and down [E, H, I]) as torch's grouped GEMM and as
+    moe_gemm.hip, alternating in one run, and the whole layer both ways.
+    torch's dA / dW are autograd's backward of F.grouped_mm with only that
+    input requiring a gradient; the hip products are the kernels themselves."""
+    k = args.top_k
+    N = xp.shape[0]
+    h = silu_mul(moe.expert_mm(xp, gate_up, offs))
+    variants, flops, check = {}, {}, {}
+    for name, a, w in (("gate_up", xp, gate_up), ("down", h, down)):
+        M, K = w.shape[1], w.shape[2]
+        g = torch.randn(N, M, device=a.device, dtype=a.dtype)
+        flops[name] = 2.0 * N * M * K
+        # the timed products agree at the timed shape: largest difference
+        # between the two implementations over the largest value
+        al, wl = a.detach().requires_grad_(), w.detach().requires_grad_()
+        ref = moe.expert_mm(al, wl, offs)
+        ref.backward(g)
+        for prod, want, got in (
+                ("fwd", ref.detach(), C.moe_gemm_rows(a, w, offs, False)),
+                ("da", al.grad, C.moe_gemm_rows(g, w, offs, True)),
+                ("dw", wl.grad, C.moe_gemm_dw(g, a, offs))):
+            check[f"{name}_{prod}_max_diff_over_max"] = round(
+                ((got.float() - want.float()).abs().max()
+                 / want.float().abs().max()).item(), 5)
+        del al, wl, ref
+        variants.update({
+            f"torch_{name}_fwd": lambda a=a, w=w: moe.expert_mm(a, w, offs),
+            f"hip_{name}_fwd":
+                lambda a=a, w=w: C.moe_gemm_rows(a, w, offs, False),
+            f"torch_{name}_da_fwd": fwd(
+                f"a{name}", lambda a_, w=w: moe.expert_mm(a_, w, offs), a),
+            f"torch_{name}_da": bwd(f"a{name}", g),
+            f"hip_{name}_da":
+                lambda g=g, w=w: C.moe_gemm_rows(g, w, offs, True),
+            f"torch_{name}_dw_fwd": fwd(
+                f"w{name}", lambda w_, a=a: moe.expert_mm(a, w_, offs), w),
+            f"torch_{name}_dw": bwd(f"w{name}", g),
+            f"hip_{name}_dw": lambda g=g, a=a: C.moe_gemm_dw(g, a, offs),
+        })
+    for impl in ("torch", "hip"):
+        variants[f"{impl}_layer_fwd"] = fwd(
+            impl, lambda *a, impl=impl: moe.moe_mlp(*a, k, True,
+                                                    expert_gemm=impl),
+            x, router_w, gate_up, down)
+        variants[f"{impl}_layer_bwd"] = bwd(impl, dy)
+    res = timed(variants, args.warmup, args.repeats)
+    res.update(check)
+    for name, fl in flops.items():
+        for pre in ("torch", "hip"):
+            for prod in ("fwd", "da", "dw"):
+                ms = res.get(f"{pre}_{name}_{prod}_ms")
+                if ms:
+                    res[f"{pre}_{name}_{prod}_tflops"] = round(
+                        fl / (ms * 1e-3) / 1e12, 1)
+    for impl in ("torch", "hip"):
+        res[f"{impl}_layer_fwdbwd_ms"] = round(
+            res[f"{impl}_layer_fwd_ms"] + res[f"{impl}_layer_bwd_ms"], 4)
+        res[f"{impl}_six_products_ms"] = round(sum(
+            res[f"{impl}_{n}_{p}_ms"] for n in flops
+            for p in ("fwd", "da", "dw")), 4)
+    rows = torch.diff(offs, prepend=offs.new_zeros(1))
+    res["rows_per_expert_min_mean_max"] = [
+        rows.min().item(), round(N / offs.numel(), 1), rows.max().item()]
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--tokens", type=int, default=24576)
@@ -129,10 +204,15 @@ def main():
     p.add_argument("--e2e-steps", type=int, default=5)
     p.add_argument("--aux", action="store_true",
                    help="time the router's auxiliary-loss variants only")
+    p.add_argument("--expert-gemm", action="store_true",
+                   help="time the expert GEMMs only: torch's grouped GEMM "
+                        "against _hip/moe_gemm.hip")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.out is None:
-        args.out = "profiles/moe_aux.json" if args.aux else "profiles/moe.json"
+        args.out = "profiles/moe_aux.json" if args.aux else \
+            "profiles/moe_gemm.json" if args.expert_gemm else \
+            "profiles/moe.json"
 
     if not torch.cuda.is_available():
         sys.exit("bench_moe needs a GPU: timings are not measured on the CPU")
@@ -244,6 +324,15 @@ def main():
         out = Path(args.out)
         out.parent.mkdir(parents=True, exist_ok=True)
         out.write_text(json.dumps({"router_aux": result}, indent=2) + "\n")
+        return
+    if args.expert_gemm:
+        del yp, dxp, dyp
+        result.update(expert_gemm_mode(args, C, moe, silu_mul, x, router_w,
+                                       gate_up, down, xp, offs, dy, fwd, bwd))
+        print(json.dumps(result))
+        out = Path(args.out)
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps({"expert_gemm": result}, indent=2) + "\n")
         return
     result.update(timed(variants, args.warmup, args.repeats))
     result["expert_gemm_path"] = moe.last_expert_mm_path
