@@ -656,6 +656,78 @@ torch::Tensor moe_gemm_dw(torch::Tensor dy, torch::Tensor a,
   return dw;
 }
 
+// ---------------- gather-fused expert GEMMs (moe_gemm_gather.hip) ---------
+// row_src int32 [T*k]: the token of every row of the expert-sorted layout
+torch::Tensor moe_row_src(torch::Tensor dest, int64_t k) {
+  TORCH_CHECK(dest.is_cuda() && dest.dtype() == torch::kInt &&
+                  dest.is_contiguous() && dest.dim() == 1,
+              "moe_row_src: dest must be contiguous int32 [T*k] on the GPU");
+  const int64_t N = dest.numel();
+  TORCH_CHECK(k >= 1 && k <= 8 && N % k == 0 && N <= INT32_MAX,
+              "moe_row_src: k must be in [1, 8] and divide dest's length");
+  auto row_src = torch::empty({N}, dest.options());
+  moe_row_src_launch(dest.data_ptr<int>(), row_src.data_ptr<int>(), N / k,
+                     (int)k, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return row_src;
+}
+
+// x [T, K] with T >= 1 wherever there is a row; row_src int32 [N]
+inline void moe_gather_check(const torch::Tensor& x,
+                             const torch::Tensor& row_src, int64_t E,
+                             int64_t M, int64_t K, const torch::Tensor& offs,
+                             const char* what) {
+  moe_gemm_check(x, E, M, K, offs, what);
+  TORCH_CHECK(x.size(1) == K, what, ": x must be [T, K]");
+  CHECK_ON_DEVICE_CONTIG(row_src, x, torch::kInt, "int32");
+  TORCH_CHECK(row_src.dim() == 1 && row_src.numel() <= INT32_MAX - 256, what,
+              ": row_src must be [N] with N < 2^31 - 256");
+  TORCH_CHECK(row_src.numel() == 0 || x.size(0) > 0, what,
+              ": rows without a token to read");
+}
+
+// y [N, M] = x[row_src[r]] . weight[e]^T per expert group of rows
+torch::Tensor moe_gemm_rows_gather(torch::Tensor x, torch::Tensor row_src,
+                                   torch::Tensor weight, torch::Tensor offs) {
+  TORCH_CHECK(weight.dim() == 3,
+              "moe_gemm_rows_gather: weight must be [E, M, K]");
+  const int64_t E = weight.size(0), M = weight.size(1), K = weight.size(2);
+  moe_gather_check(x, row_src, E, M, K, offs, "moe_gemm_rows_gather");
+  CHECK_ON_DEVICE_CONTIG(weight, x, torch::kBFloat16, "bf16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0,
+              "moe_gemm_rows_gather: weight must be 16-byte aligned");
+  const int64_t N = row_src.numel();
+  TORCH_CHECK((N / 128 + 1 + E) * (M / 128 + 1) <= INT32_MAX,
+              "moe_gemm_rows_gather: too many tiles for one grid");
+  auto out = torch::empty({N, M}, x.options());
+  moe_gemm_rows_gather_launch(x.data_ptr(), row_src.data_ptr<int>(),
+                              weight.data_ptr(), offs.data_ptr<int>(),
+                              out.data_ptr(), N, x.size(0), (int)E, (int)M,
+                              (int)K, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return out;
+}
+
+// dw [E, M, K] = dy[rows of e]^T . x[row_src[rows of e]]
+torch::Tensor moe_gemm_dw_gather(torch::Tensor dy, torch::Tensor x,
+                                 torch::Tensor row_src, torch::Tensor offs) {
+  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 &&
+                  dy.size(0) == row_src.numel(),
+              "moe_gemm_dw_gather: dy [N, M], x [T, K], row_src [N]");
+  const int64_t E = offs.numel(), M = dy.size(1), K = x.size(1);
+  moe_gemm_check(dy, E, M, K, offs, "moe_gemm_dw_gather");
+  moe_gather_check(x, row_src, E, M, K, offs, "moe_gemm_dw_gather");
+  TORCH_CHECK(E * (M / 128 + 1) * (K / 128 + 1) <= INT32_MAX,
+              "moe_gemm_dw_gather: too many tiles for one grid");
+  auto dw = torch::empty({E, M, K}, x.options());
+  moe_gemm_dw_gather_launch(dy.data_ptr(), x.data_ptr(),
+                            row_src.data_ptr<int>(), offs.data_ptr<int>(),
+                            dw.data_ptr(), dy.size(0), x.size(0), (int)E,
+                            (int)M, (int)K, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dw;
+}
+
 // ---------------- silu_mul ----------------
 torch::Tensor silu_mul_fwd(torch::Tensor gu) {
   CHECK_BF16_CONTIG(gu);
@@ -1206,6 +1278,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine_bwd", &moe_combine_bwd);
   m.def("moe_gemm_rows", &moe_gemm_rows);
   m.def("moe_gemm_dw", &moe_gemm_dw);
+  m.def("moe_row_src", &moe_row_src);
+  m.def("moe_gemm_rows_gather", &moe_gemm_rows_gather);
+  m.def("moe_gemm_dw_gather", &moe_gemm_dw_gather);
   m.def("silu_mul_fwd", &silu_mul_fwd);
   m.def("silu_mul_bwd", &silu_mul_bwd);
   m.def("embedding_fwd", &embedding_fwd);

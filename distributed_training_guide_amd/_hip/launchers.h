@@ -147,6 +147,26 @@ void moe_gemm_dw_launch(const void* dy, const void* a, const int* offs,
                         void* dw, int64_t N, int E, int M, int K,
                         hipStream_t s);
 
+// moe_gemm_gather.hip: the forward and dW of moe_gemm.hip with the token
+// operand read through a row index instead of from the expert-sorted copy.
+// x [T, K] bf16, 16 B aligned; row_src int32 [N], the token of every sorted
+// row (values outside [0, T) are clamped); the rest as above.
+// moe_row_src_launch: row_src[dest[t*k + j]] = t for dest int32 [T*k], a
+// permutation of [0, T*k), k <= 8; every element written once.
+// moe_gemm_rows_gather_launch: out [N, M] = x[row_src[r]] . weight[e]^T.
+// moe_gemm_dw_gather_launch: dw [E, M, K] = dy[rows of e]^T .
+// x[row_src[rows of e]], every element written once.
+void moe_row_src_launch(const int* dest, int* row_src, int64_t T, int k,
+                        hipStream_t s);
+void moe_gemm_rows_gather_launch(const void* x, const int* row_src,
+                                 const void* weight, const int* offs,
+                                 void* out, int64_t N, int64_t T, int E, int M,
+                                 int K, hipStream_t s);
+void moe_gemm_dw_gather_launch(const void* dy, const void* x,
+                               const int* row_src, const int* offs, void* dw,
+                               int64_t N, int64_t T, int E, int M, int K,
+                               hipStream_t s);
+
 // embedding.hip
 void embed_fwd_launch(const void* table, const int64_t* ids, void* out,
                       int64_t nrows, int H, int64_t V, hipStream_t s);

@@ -67,7 +67,9 @@ class LlamaConfig:
     router_aux_loss_coef: float = 0.0
     router_z_loss_coef: float = 0.0
     # the expert GEMMs (ops/moe.py expert_mm): "torch" is torch's grouped
-    # GEMM, "hip" the hand-written grouped GEMMs of _hip/moe_gemm.hip
+    # GEMM, "hip" the hand-written grouped GEMMs of _hip/moe_gemm.hip,
+    # "hip-gather" those without the expert-sorted copy of the tokens
+    # (_hip/moe_gemm_gather.hip)
     expert_gemm: str = "torch"
 
     @property

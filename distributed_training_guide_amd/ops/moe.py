@@ -11,7 +11,9 @@ back, each with its backward.  No host sync, no atomics (so no
 non-deterministic index_add_), no cleared buffers.  The expert GEMMs have a
 hand-written alternative as well, opt-in: expert_mm(impl="hip") /
 moe_mlp(expert_gemm="hip") run the grouped bf16 MFMA GEMMs of moe_gemm.hip,
-forward and backward.
+forward and backward; "hip-gather" also drops the scattered copy of the
+tokens, the gate_up GEMM reading them through a row index
+(moe_gemm_gather.hip).
 
 Layout.  Slot s = t*k + j is token t's j-th selected expert.  `dest[s]` is
 the slot's row in the expert-sorted layout (rows of one expert contiguous,
@@ -248,13 +250,23 @@ def moe_combine(yp, dest, w):
 # --------------------------------------------------------------------------
 # expert GEMMs and the composed layer
 # --------------------------------------------------------------------------
-# "grouped", "loop" or "hip": which path the last expert_mm call took
+# "grouped", "loop", "hip" or "hip-gather": which path the last expert_mm
+# call took
 # (reporting only; the torch decision is kept per device type in
 # _grouped_mm_works)
 last_expert_mm_path = None
 _grouped_mm_works = {}  # device type -> bool, decided by the first call
-EXPERT_GEMM_IMPLS = ("torch", "hip")
+EXPERT_GEMM_IMPLS = ("torch", "hip", "hip-gather")
 MOE_GEMM_MAX_EXPERTS = 128
+
+
+def moe_row_src(dest, k):
+    """row_src int32 [T*k]: the token of every row of the expert-sorted
+    layout, row_src[dest[t*k + j]] = t.  What the gather-fused expert GEMMs
+    read x through instead of a scattered copy."""
+    if use_hip(dest):
+        return ext().moe_row_src(dest.contiguous(), int(k))
+    return _rows_of(dest, k)[1].to(torch.int32)
 
 
 def _expert_mm_loop(a, weight, offs):
@@ -286,6 +298,34 @@ class _ExpertMMFn(torch.autograd.Function):
         return da, dw, None
 
 
+class _ExpertMMGatherFn(torch.autograd.Function):
+    """_ExpertMMFn on the unsorted tokens x [T, K] (moe_gemm_gather.hip):
+    y[r] = x[row_src[r]] . w[e]^T.  Saves x, which the router projection
+    keeps alive anyway, and never an [N, K] tensor; row_src is 4 bytes a row
+    and one small launch, so the backward rebuilds it from dest rather than
+    keep it.  dx is the k-way sum of the sorted dxp (the scatter's backward),
+    dw reads x through row_src again."""
+
+    @staticmethod
+    def forward(ctx, x, weight, offs, dest, row_src):
+        ctx.save_for_backward(x, weight, offs, dest)
+        return ext().moe_gemm_rows_gather(x, row_src, weight, offs)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, offs, dest = ctx.saved_tensors
+        dy = dy.contiguous()
+        k = dest.numel() // x.shape[0]
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dxp = ext().moe_gemm_rows(dy, weight, offs, True)
+            dx = ext().moe_combine(dxp, dest, None, k)
+        if ctx.needs_input_grad[1]:
+            dw = ext().moe_gemm_dw_gather(dy, x, ext().moe_row_src(dest, k),
+                                          offs)
+        return dx, dw, None, None, None
+
+
 def moe_gemm_supported(a, weight):
     """What moe_gemm.hip serves: bf16 on the GPU, E <= 128, M and K
     multiples of 64 (any N, any rows per expert)."""
@@ -295,7 +335,7 @@ def moe_gemm_supported(a, weight):
         and M >= 64 and M % 64 == 0 and K >= 64 and K % 64 == 0
 
 
-def expert_mm(a, weight, offs, impl="torch"):
+def expert_mm(a, weight, offs, impl="torch", row_src=None, dest=None):
     """Rows [offs[e-1], offs[e]) of a [N, K] times weight[e].T, for weight
     [E, M, K]: the one helper both expert GEMMs go through.  torch's grouped
     GEMM takes the device-side offsets, so nothing waits on the host.
@@ -304,6 +344,16 @@ def expert_mm(a, weight, offs, impl="torch"):
     and backward, where moe_gemm_supported holds (no host read of offs, no
     dependence on torch's grouped GEMM); on a CPU tensor or another shape or
     dtype it is the torch path below, unchanged.
+
+    With `row_src` (moe_row_src) and the `dest` it was built from, a is the
+    unsorted [T, K] token tensor and row r of the product is
+    a[row_src[r]] . weight[e].T.  impl="hip-gather" then runs the kernels of
+    moe_gemm_gather.hip, which read a through row_src in the forward and in
+    the weight gradient, so no [N, K] copy is made or saved; the results are
+    the bits impl="hip" gives on moe_scatter(a, dest, k).  Where
+    moe_gemm_supported fails, or under another impl, the rows are scattered
+    first and the call goes on as without row_src.  Without row_src
+    "hip-gather" is "hip".
 
     Where this build of torch cannot run the grouped GEMM on a's kind of
     device, the helper warns once and from then on loops over the experts'
@@ -321,7 +371,19 @@ def expert_mm(a, weight, offs, impl="torch"):
             f"expert_mm: a [N, K], weight [E, M, K], offs int32 [E]; got "
             f"{tuple(a.shape)}, {tuple(weight.shape)}, {tuple(offs.shape)} "
             f"{offs.dtype}")
-    if impl == "hip" and moe_gemm_supported(a, weight):
+    if row_src is not None:
+        if dest is None or a.shape[0] < 1 or row_src.shape != dest.shape \
+                or dest.dim() != 1 or dest.numel() % a.shape[0] != 0:
+            raise ValueError(
+                "expert_mm: with row_src, a is [T, K] with T >= 1 and "
+                "row_src and dest are both [T*k]")
+        if impl == "hip-gather" and moe_gemm_supported(a, weight):
+            last_expert_mm_path = "hip-gather"
+            return _ExpertMMGatherFn.apply(a.contiguous(),
+                                           weight.contiguous(), offs, dest,
+                                           row_src)
+        a = moe_scatter(a, dest, dest.numel() // a.shape[0])
+    if impl != "torch" and moe_gemm_supported(a, weight):
         last_expert_mm_path = "hip"
         return _ExpertMMFn.apply(a.contiguous(), weight.contiguous(), offs)
     kind = a.device.type
@@ -353,8 +415,15 @@ def _mlp_chain(x, router_weight, gate_up, down, k, norm, aux, router, index,
     idx, w, *losses = router(logits, k, norm, True) if aux \
         else router(logits, k, norm)
     dest, offs = index(idx, E)
-    xp = scatter(x, dest, k)
-    h = silu_mul(expert_mm(xp, gate_up, offs, expert_gemm))
+    if expert_gemm == "hip-gather" and x.shape[0] > 0 \
+            and moe_gemm_supported(x, gate_up):
+        # gate_up reads x through the row index; h is born sorted, so the
+        # down GEMM below is the plain "hip" one
+        gu = expert_mm(x, gate_up, offs, expert_gemm,
+                       row_src=moe_row_src(dest, k), dest=dest)
+    else:
+        gu = expert_mm(scatter(x, dest, k), gate_up, offs, expert_gemm)
+    h = silu_mul(gu)
     y = combine(expert_mm(h, down, offs, expert_gemm), dest, w)
     return (y, *losses) if aux else y
 
@@ -378,7 +447,11 @@ def moe_mlp(x, router_weight, gate_up, down, k, norm_topk_prob=True,
     goes through its k routed experts and the outputs are summed with the
     router's weights.  With `aux` it returns (y, aux, z), the router's two
     auxiliary losses over these tokens (moe_router).  `expert_gemm` is
-    expert_mm's `impl` for both expert GEMMs."""
+    expert_mm's `impl` for both expert GEMMs.  "hip-gather" is "hip" without
+    the scattered copy of x: the gate_up GEMM and its weight gradient read x
+    through moe_row_src's index (moe_gemm_gather.hip), which keeps T*k*H
+    bf16 less alive until the backward; outputs and gradients are the same
+    bits."""
     if expert_gemm not in EXPERT_GEMM_IMPLS:
         raise ValueError(f"moe_mlp: expert_gemm must be one of "
                          f"{EXPERT_GEMM_IMPLS}, got {expert_gemm!r}")

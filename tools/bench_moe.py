@@ -39,6 +39,12 @@ gate_up and the down GEMM as torch's grouped GEMM and as moe_gemm.hip, with
 the achieved TFLOP/s from the shapes (2 N M K per product), and the whole
 layer forward + backward with either.
 
+--gather times expert_gemm="hip-gather" against "hip" instead (default --out
+profiles/moe_gemm_gather.json), alternating in one run: the gate_up forward
+of moe_gemm_gather.hip against scatter + forward, the gate_up dW both ways,
+the row index build, the whole layer forward + backward, and the memory a
+layer holds after its forward and at its peak.
+
 --e2e-layers L additionally times training steps of a cut-down model of the
 same layer shape with L layers (the 30B model's 366 GB of parameter and
 optimizer state do not fit one GPU).  Results go to --out; no threshold is
@@ -191,6 +197,60 @@ def expert_gemm_mode(args, C, moe, silu_mul, x, router_w, gate_up, down, xp,
     return res
 
 
+def gather_mode(args, C, moe, x, router_w, gate_up, down, dest, offs, dy, fwd,
+                bwd):
+    """expert_gemm="hip-gather" against "hip", alternating in one run: the
+    gate_up forward reading x through row_src against scatter + forward on
+    the copy, the gate_up dW both ways, the row index build, the whole layer
+    forward + backward, and the peak allocation of one layer step above what
+    is allocated before it."""
+    k = args.top_k
+    N = dest.numel()
+    row_src = C.moe_row_src(dest, k)
+    xp = C.moe_scatter(x, dest)
+    g = torch.randn(N, gate_up.shape[1], device=x.device, dtype=x.dtype)
+    same = {
+        "fwd_equal": torch.equal(
+            C.moe_gemm_rows_gather(x, row_src, gate_up, offs),
+            C.moe_gemm_rows(xp, gate_up, offs, False)),
+        "dw_equal": torch.equal(C.moe_gemm_dw_gather(g, x, row_src, offs),
+                                C.moe_gemm_dw(g, xp, offs)),
+    }
+    variants = {
+        "row_src": (lambda: C.moe_row_src(dest, k), SMALL_OP_LAUNCHES),
+        "hip_scatter_fwd": lambda: C.moe_gemm_rows(
+            C.moe_scatter(x, dest), gate_up, offs, False),
+        "gather_fwd": lambda: C.moe_gemm_rows_gather(x, row_src, gate_up,
+                                                     offs),
+        "hip_dw": lambda: C.moe_gemm_dw(g, xp, offs),
+        "gather_dw": lambda: C.moe_gemm_dw_gather(g, x, row_src, offs),
+    }
+    for impl in ("hip", "hip-gather"):
+        variants[f"{impl}_layer_fwd"] = fwd(
+            impl, lambda *a, impl=impl: moe.moe_mlp(*a, k, True,
+                                                    expert_gemm=impl),
+            x, router_w, gate_up, down)
+        variants[f"{impl}_layer_bwd"] = bwd(impl, dy)
+    res = timed(variants, args.warmup, args.repeats)
+    res.update(same)
+    del xp, g
+    for impl in ("hip", "hip-gather"):
+        res[f"{impl}_layer_fwdbwd_ms"] = round(
+            res[f"{impl}_layer_fwd_ms"] + res[f"{impl}_layer_bwd_ms"], 4)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        variants[f"{impl}_layer_fwd"]()
+        held = torch.cuda.memory_allocated() - base
+        variants[f"{impl}_layer_bwd"]()
+        torch.cuda.synchronize()
+        res[f"{impl}_layer_held_after_fwd_mb"] = round(held / 1e6, 1)
+        res[f"{impl}_layer_peak_mb"] = round(
+            (torch.cuda.max_memory_allocated() - base) / 1e6, 1)
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--tokens", type=int, default=24576)
@@ -207,11 +267,15 @@ def main():
     p.add_argument("--expert-gemm", action="store_true",
                    help="time the expert GEMMs only: torch's grouped GEMM "
                         "against _hip/moe_gemm.hip")
+    p.add_argument("--gather", action="store_true",
+                   help="time expert_gemm='hip-gather' "
+                        "(_hip/moe_gemm_gather.hip) against 'hip'")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.out is None:
         args.out = "profiles/moe_aux.json" if args.aux else \
             "profiles/moe_gemm.json" if args.expert_gemm else \
+            "profiles/moe_gemm_gather.json" if args.gather else \
             "profiles/moe.json"
 
     if not torch.cuda.is_available():
@@ -333,6 +397,15 @@ def main():
         out = Path(args.out)
         out.parent.mkdir(parents=True, exist_ok=True)
         out.write_text(json.dumps({"expert_gemm": result}, indent=2) + "\n")
+        return
+    if args.gather:
+        del yp, dxp, dyp, xp
+        result.update(gather_mode(args, C, moe, x, router_w, gate_up, down,
+                                  dest, offs, dy, fwd, bwd))
+        print(json.dumps(result))
+        out = Path(args.out)
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps({"gather": result}, indent=2) + "\n")
         return
     result.update(timed(variants, args.warmup, args.repeats))
     result["expert_gemm_path"] = moe.last_expert_mm_path
