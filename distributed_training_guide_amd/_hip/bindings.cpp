@@ -728,6 +728,95 @@ torch::Tensor moe_gemm_dw_gather(torch::Tensor dy, torch::Tensor x,
   return dw;
 }
 
+// ---------------- weighted-SwiGLU expert GEMMs (moe_gemm_swiglu.hip) -------
+// w_row f32 [T*k]: the router weight of every row of the expert-sorted layout
+torch::Tensor moe_row_w(torch::Tensor dest, torch::Tensor topk_w) {
+  TORCH_CHECK(dest.is_cuda() && dest.dtype() == torch::kInt &&
+                  dest.is_contiguous() && dest.dim() == 1,
+              "moe_row_w: dest must be contiguous int32 [T*k] on the GPU");
+  CHECK_ON_DEVICE_CONTIG(topk_w, dest, torch::kFloat, "f32");
+  const int64_t N = dest.numel();
+  TORCH_CHECK(topk_w.dim() == 2 && topk_w.numel() == N &&
+                  topk_w.size(1) >= 1 && topk_w.size(1) <= 8 &&
+                  N <= INT32_MAX,
+              "moe_row_w: topk_w must be [T, k] with k in [1, 8], dest [T*k]");
+  auto w_row = torch::empty({N}, topk_w.options());
+  moe_row_w_launch(dest.data_ptr<int>(), topk_w.data_ptr<float>(),
+                   w_row.data_ptr<float>(), topk_w.size(0),
+                   (int)topk_w.size(1), cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return w_row;
+}
+
+// (gu [N, 2I], h' [N, I]) of gate_up [E, 2I, K] on x [T, K] through row_src
+std::vector<torch::Tensor> moe_gemm_gu_swiglu(torch::Tensor x,
+                                              torch::Tensor row_src,
+                                              torch::Tensor w_row,
+                                              torch::Tensor gate_up,
+                                              torch::Tensor offs) {
+  TORCH_CHECK(gate_up.dim() == 3,
+              "moe_gemm_gu_swiglu: gate_up must be [E, 2I, K]");
+  const int64_t E = gate_up.size(0), M = gate_up.size(1), K = gate_up.size(2);
+  moe_gather_check(x, row_src, E, M, K, offs, "moe_gemm_gu_swiglu");
+  TORCH_CHECK(M % 128 == 0, "moe_gemm_gu_swiglu: I must be a multiple of 64");
+  CHECK_ON_DEVICE_CONTIG(gate_up, x, torch::kBFloat16, "bf16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(gate_up.data_ptr()) % 16 == 0,
+              "moe_gemm_gu_swiglu: gate_up must be 16-byte aligned");
+  const int64_t N = row_src.numel(), I = M / 2;
+  CHECK_ON_DEVICE_CONTIG(w_row, x, torch::kFloat, "f32");
+  TORCH_CHECK(w_row.dim() == 1 && w_row.numel() == N,
+              "moe_gemm_gu_swiglu: w_row must be [N]");
+  TORCH_CHECK((N / 128 + 1 + E) * (I / 64) <= INT32_MAX,
+              "moe_gemm_gu_swiglu: too many tiles for one grid");
+  auto gu = torch::empty({N, M}, x.options());
+  auto hw = torch::empty({N, I}, x.options());
+  moe_gemm_gu_swiglu_launch(x.data_ptr(), row_src.data_ptr<int>(),
+                            w_row.data_ptr<float>(), gate_up.data_ptr(),
+                            offs.data_ptr<int>(), gu.data_ptr(), hw.data_ptr(),
+                            N, x.size(0), (int)E, (int)I, (int)K,
+                            cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {gu, hw};
+}
+
+// (dgu [N, 2I], dw_topk f32 [N]) from dyp [N, H], down [E, H, I], the saved
+// gu [N, 2I], w_row [N] and dest [N]
+std::vector<torch::Tensor> moe_gemm_da_swiglu(torch::Tensor dyp,
+                                              torch::Tensor down,
+                                              torch::Tensor gu,
+                                              torch::Tensor w_row,
+                                              torch::Tensor offs,
+                                              torch::Tensor dest) {
+  TORCH_CHECK(down.dim() == 3, "moe_gemm_da_swiglu: down must be [E, H, I]");
+  const int64_t E = down.size(0), H = down.size(1), I = down.size(2);
+  moe_gemm_check(dyp, E, H, I, offs, "moe_gemm_da_swiglu");
+  moe_gemm_check(gu, E, H, I, offs, "moe_gemm_da_swiglu");
+  CHECK_ON_DEVICE_CONTIG(down, dyp, torch::kBFloat16, "bf16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(down.data_ptr()) % 16 == 0,
+              "moe_gemm_da_swiglu: down must be 16-byte aligned");
+  const int64_t N = dyp.size(0);
+  TORCH_CHECK(dyp.size(1) == H && gu.size(0) == N && gu.size(1) == 2 * I &&
+                  gu.device() == dyp.device(),
+              "moe_gemm_da_swiglu: dyp [N, H] and gu [N, 2I]");
+  CHECK_ON_DEVICE_CONTIG(w_row, dyp, torch::kFloat, "f32");
+  CHECK_ON_DEVICE_CONTIG(dest, dyp, torch::kInt, "int32");
+  TORCH_CHECK(w_row.dim() == 1 && w_row.numel() == N && dest.dim() == 1 &&
+                  dest.numel() == N,
+              "moe_gemm_da_swiglu: w_row and dest must be [N]");
+  TORCH_CHECK((N / 128 + 1 + E) * (I / 128 + 1) <= INT32_MAX,
+              "moe_gemm_da_swiglu: too many tiles for one grid");
+  auto dgu = torch::empty_like(gu);
+  auto dwp = torch::empty({N, moe_dw_parts((int)I)}, w_row.options());
+  auto dw = torch::empty({N}, w_row.options());
+  moe_gemm_da_swiglu_launch(dyp.data_ptr(), down.data_ptr(), gu.data_ptr(),
+                            w_row.data_ptr<float>(), offs.data_ptr<int>(),
+                            dest.data_ptr<int>(), dgu.data_ptr(),
+                            dwp.data_ptr<float>(), dw.data_ptr<float>(), N,
+                            (int)E, (int)H, (int)I, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {dgu, dw};
+}
+
 // ---------------- silu_mul ----------------
 torch::Tensor silu_mul_fwd(torch::Tensor gu) {
   CHECK_BF16_CONTIG(gu);
@@ -1281,6 +1370,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_row_src", &moe_row_src);
   m.def("moe_gemm_rows_gather", &moe_gemm_rows_gather);
   m.def("moe_gemm_dw_gather", &moe_gemm_dw_gather);
+  m.def("moe_row_w", &moe_row_w);
+  m.def("moe_gemm_gu_swiglu", &moe_gemm_gu_swiglu);
+  m.def("moe_gemm_da_swiglu", &moe_gemm_da_swiglu);
   m.def("silu_mul_fwd", &silu_mul_fwd);
   m.def("silu_mul_bwd", &silu_mul_bwd);
   m.def("embedding_fwd", &embedding_fwd);

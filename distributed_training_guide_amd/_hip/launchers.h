@@ -167,6 +167,32 @@ void moe_gemm_dw_gather_launch(const void* dy, const void* x,
                                int64_t N, int64_t T, int E, int M, int K,
                                hipStream_t s);
 
+// moe_gemm_swiglu.hip: the gate_up forward and the down dA with the weighted
+// SwiGLU in their epilogues.  gate_up [E, 2I, K], down [E, H, I], I, K and H
+// multiples of 64; w_row f32 [N], the router weight of every sorted row; the
+// rest as above.
+// moe_row_w_launch: w_row[dest[t*k + j]] = topk_w[t, j], k <= 8.
+// moe_gemm_gu_swiglu_launch: gu [N, 2I] = x[row_src[r]] . gate_up[e]^T (the
+// bits of moe_gemm_rows_gather_launch) and hw [N, I] = w_row * silu(g) * u
+// from the rounded gu.
+// moe_gemm_da_swiglu_launch: from dyp [N, H] and the saved gu, dgu [N, 2I]
+// (the SwiGLU backward of w_row * (dyp . down[e]), which is never written)
+// and dw_topk f32 [N], dw_topk[s] = <dyp . down[e], silu(g) * u> of row
+// dest[s].  dwp is N * moe_dw_parts(I) f32 of scratch that needs no
+// initialisation.
+void moe_row_w_launch(const int* dest, const float* topk_w, float* w_row,
+                      int64_t T, int k, hipStream_t s);
+void moe_gemm_gu_swiglu_launch(const void* x, const int* row_src,
+                               const float* w_row, const void* gate_up,
+                               const int* offs, void* gu, void* hw, int64_t N,
+                               int64_t T, int E, int I, int K, hipStream_t s);
+int moe_dw_parts(int I);
+void moe_gemm_da_swiglu_launch(const void* dyp, const void* down,
+                               const void* gu, const float* w_row,
+                               const int* offs, const int* dest, void* dgu,
+                               float* dwp, float* dw_topk, int64_t N, int E,
+                               int H, int I, hipStream_t s);
+
 // embedding.hip
 void embed_fwd_launch(const void* table, const int64_t* ids, void* out,
                       int64_t nrows, int H, int64_t V, hipStream_t s);

@@ -58,26 +58,6 @@ __global__ void __launch_bounds__(256) moe_row_src_kernel(
   }
 }
 
-// A lane's element offset into x for the source token `t` of a sorted row,
-// clamped into [0, T): the token's row plus the lane's 8 columns of the
-// wave's 16-column subtile.
-__device__ __forceinline__ int64_t src_off(int t, int T, int64_t stride,
-                                           int wid, int lane) {
-  return (int64_t)min(max(t, 0), T - 1) * stride + wid * 16 + (lane & 1) * 8;
-}
-
-// stage_img with the lane's two rows given as element offsets from g: chunk
-// wid*2 + j lands at the same place of the image.
-__device__ __forceinline__ void stage_img_at(const short* g,
-                                             const int64_t (&off)[2],
-                                             short* img, int wid) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)(g + off[j]),
-        (LDS_AS unsigned int*)(img + (wid * 2 + j) * 512), 16, 0, 0);
-}
-
 // out[r, :] = x[row_src[r], :] . weight[e]^T for the rows r of group e:
 // x [T, L], weight [E, C, L], out [N, C].  Grid as moe_gemm_rows_kernel.
 __global__ void __launch_bounds__(256, 2) moe_gemm_rows_gather_kernel(

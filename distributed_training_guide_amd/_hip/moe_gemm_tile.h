@@ -1,8 +1,9 @@
 // The 128 x 128 output tile of the grouped expert GEMMs (moe_gemm.hip,
-// moe_gemm_gather.hip): the LDS-DMA staging of one 64 x 64 st_idx image, the
-// 64-deep MFMA step of a wave's 64 x 64 quarter, its store, and the search of
-// the expert-major list of row tiles.  The structure is described at the top
-// of moe_gemm.hip.
+// moe_gemm_gather.hip, moe_gemm_swiglu.hip): the LDS-DMA staging of one
+// 64 x 64 st_idx image (by row range or through a row index), the 64-deep
+// MFMA step of a wave's 64 x 64 quarter, its store, and the search of the
+// expert-major list of row tiles.  The structure is described at the top of
+// moe_gemm.hip.
 #pragma once
 #include "attention_common.h"
 
@@ -29,6 +30,26 @@ __device__ __forceinline__ void stage_img(const short* g, int64_t stride,
         (const __attribute__((address_space(1))) unsigned int*)(g + goff),
         (LDS_AS unsigned int*)(img + ch * 512), 16, 0, 0);
   }
+}
+
+// A lane's element offset into x for the source token `t` of a sorted row,
+// clamped into [0, T): the token's row plus the lane's 8 columns of the
+// wave's 16-column subtile.
+__device__ __forceinline__ int64_t src_off(int t, int T, int64_t stride,
+                                           int wid, int lane) {
+  return (int64_t)min(max(t, 0), T - 1) * stride + wid * 16 + (lane & 1) * 8;
+}
+
+// stage_img with the lane's two rows given as element offsets from g: chunk
+// wid*2 + j lands at the same place of the image.
+__device__ __forceinline__ void stage_img_at(const short* g,
+                                             const int64_t (&off)[2],
+                                             short* img, int wid) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)(g + off[j]),
+        (LDS_AS unsigned int*)(img + (wid * 2 + j) * 512), 16, 0, 0);
 }
 
 // One 64-deep contraction step of a wave's 64 x 64 quarter.  rimg / cimg are
@@ -69,6 +90,35 @@ __device__ __forceinline__ void mma_step(const short* rimg, const short* cimg,
           rf[t] = __builtin_bit_cast(
               bf16x8, __builtin_bit_cast(u32x4, rf[t]) & m);
       }
+    }
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt)
+        acc[ct][rt] = mfma16(cf[ct], rf[rt], acc[ct][rt]);
+  }
+}
+
+// mma_step<false, false> with the wave's column fragments taken from two
+// images: ct 0, 1 from rows crow + ct*16 + l15 of cimg_a, ct 2, 3 from the
+// same rows of cimg_b.  With the gate rows of a weight in cimg_a and the
+// matching up rows in cimg_b (moe_gemm_swiglu.hip) a lane holds g in
+// acc[ct][rt] and u in acc[ct + 2][rt] of the same (row, column).
+__device__ __forceinline__ void mma_step_pair(const short* rimg,
+                                              const short* cimg_a,
+                                              const short* cimg_b, int crow,
+                                              f32x4 (&acc)[4][4], int l15,
+                                              int lg) {
+#pragma unroll
+  for (int kc = 0; kc < 2; ++kc) {
+    const int k0 = kc * 32 + lg * 8;
+    bf16x8 rf[4], cf[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      rf[t] = *reinterpret_cast<const bf16x8*>(
+          rimg + st_idx(t * 16 + l15, k0));
+      cf[t] = *reinterpret_cast<const bf16x8*>(
+          (t < 2 ? cimg_a : cimg_b) + st_idx(crow + (t & 1) * 16 + l15, k0));
     }
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)

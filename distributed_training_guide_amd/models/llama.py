@@ -69,7 +69,8 @@ class LlamaConfig:
     # the expert GEMMs (ops/moe.py expert_mm): "torch" is torch's grouped
     # GEMM, "hip" the hand-written grouped GEMMs of _hip/moe_gemm.hip,
     # "hip-gather" those without the expert-sorted copy of the tokens
-    # (_hip/moe_gemm_gather.hip)
+    # (_hip/moe_gemm_gather.hip), "hip-fused" those with the weighted SwiGLU
+    # in the GEMMs' epilogues (_hip/moe_gemm_swiglu.hip)
     expert_gemm: str = "torch"
 
     @property

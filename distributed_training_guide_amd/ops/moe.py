@@ -13,7 +13,14 @@ hand-written alternative as well, opt-in: expert_mm(impl="hip") /
 moe_mlp(expert_gemm="hip") run the grouped bf16 MFMA GEMMs of moe_gemm.hip,
 forward and backward; "hip-gather" also drops the scattered copy of the
 tokens, the gate_up GEMM reading them through a row index
-(moe_gemm_gather.hip).
+(moe_gemm_gather.hip); "hip-fused" also moves the activation into the GEMMs'
+epilogues as a weighted SwiGLU (moe_gemm_swiglu.hip): the gate_up GEMM
+writes h' = w * silu(g) * u beside gu, w the row's router weight, so the
+combine is an unweighted k-way sum that saves nothing but dest, and the down
+GEMM's dA turns into d gate_up-output and the router-weight gradient while
+dh is still in accumulators.  The same layer, since row scaling commutes
+with the down projection; the rounding differs (w meets h before the GEMM,
+not its output after).
 
 Layout.  Slot s = t*k + j is token t's j-th selected expert.  `dest[s]` is
 the slot's row in the expert-sorted layout (rows of one expert contiguous,
@@ -250,13 +257,13 @@ def moe_combine(yp, dest, w):
 # --------------------------------------------------------------------------
 # expert GEMMs and the composed layer
 # --------------------------------------------------------------------------
-# "grouped", "loop", "hip" or "hip-gather": which path the last expert_mm
-# call took
+# "grouped", "loop", "hip", "hip-gather" or "hip-fused" (set by moe_mlp's fused
+# chain): which path the last expert GEMM took
 # (reporting only; the torch decision is kept per device type in
 # _grouped_mm_works)
 last_expert_mm_path = None
 _grouped_mm_works = {}  # device type -> bool, decided by the first call
-EXPERT_GEMM_IMPLS = ("torch", "hip", "hip-gather")
+EXPERT_GEMM_IMPLS = ("torch", "hip", "hip-gather", "hip-fused")
 MOE_GEMM_MAX_EXPERTS = 128
 
 
@@ -267,6 +274,18 @@ def moe_row_src(dest, k):
     if use_hip(dest):
         return ext().moe_row_src(dest.contiguous(), int(k))
     return _rows_of(dest, k)[1].to(torch.int32)
+
+
+def moe_row_w(dest, topk_w):
+    """w_row f32 [T*k]: the router weight of every row of the expert-sorted
+    layout, w_row[dest[t*k + j]] = topk_w[t, j].  Carries no gradient: the
+    fused chain forms topk_w's gradient itself."""
+    if use_hip(dest):
+        return ext().moe_row_w(dest.contiguous(),
+                               topk_w.detach().float().contiguous())
+    out = torch.empty(dest.numel(), dtype=torch.float32, device=dest.device)
+    out[dest.long()] = topk_w.detach().float().reshape(-1)
+    return out
 
 
 def _expert_mm_loop(a, weight, offs):
@@ -326,6 +345,68 @@ class _ExpertMMGatherFn(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
+class _GateUpSwigluFn(_ExpertMMGatherFn):
+    """_ExpertMMGatherFn for gate_up with the weighted SwiGLU in the epilogue
+    (moe_gemm_swiglu.hip): (gu, h') with gu[r] = x[row_src[r]] . gate_up[e]^T,
+    the bits of that function, and h' = bf16(w_r * silu(g_r) * u_r).  h' is
+    not differentiable here: _DownSwigluFn, the one place it goes, hands back
+    the gradient of gu, which the inherited backward takes to dx and the
+    weight gradient.  topk_w's gradient comes from there as well."""
+
+    @staticmethod
+    def forward(ctx, x, gate_up, topk_w, offs, dest):
+        k = topk_w.shape[1]
+        gu, hw = ext().moe_gemm_gu_swiglu(
+            x, ext().moe_row_src(dest, k), ext().moe_row_w(dest, topk_w),
+            gate_up, offs)
+        ctx.save_for_backward(x, gate_up, offs, dest)
+        ctx.mark_non_differentiable(hw)
+        return gu, hw
+
+    @staticmethod
+    def backward(ctx, dgu, _dhw):
+        return _ExpertMMGatherFn.backward(ctx, dgu)
+
+
+class _DownSwigluFn(torch.autograd.Function):
+    """yp = h' . down[e]^T as a function of gu, w and down, h' being
+    w * silu(g) * u: the rows come out sorted and already weighted.  Saves gu
+    and h', never yp and never dh: the backward's dA kernel turns
+    dyp . down[e] into dgu and topk_w's gradient in its epilogue.  w_row is
+    one small launch and is rebuilt rather than kept.  A function of its own,
+    so that dyp is released before the gate_up backward allocates."""
+
+    @staticmethod
+    def forward(ctx, gu, hw, down, topk_w, offs, dest):
+        ctx.save_for_backward(gu, hw, down, topk_w, offs, dest)
+        return ext().moe_gemm_rows(hw, down, offs, False)
+
+    @staticmethod
+    def backward(ctx, dyp):
+        gu, hw, down, topk_w, offs, dest = ctx.saved_tensors
+        dyp = dyp.contiguous()
+        dgu, dw = ext().moe_gemm_da_swiglu(
+            dyp, down, gu, ext().moe_row_w(dest, topk_w), offs, dest)
+        ddown = ext().moe_gemm_dw(dyp, hw, offs) \
+            if ctx.needs_input_grad[2] else None
+        return dgu, None, ddown, dw.view_as(topk_w), None, None
+
+
+class _SumFn(torch.autograd.Function):
+    """The unweighted combine, y[t] = sum_j yp[dest[t*k + j]]: _ScatterFn's
+    mirror.  Saves dest alone."""
+
+    @staticmethod
+    def forward(ctx, yp, dest, k):
+        ctx.save_for_backward(dest)
+        return ext().moe_combine(yp, dest, None, k)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (dest,) = ctx.saved_tensors
+        return ext().moe_scatter(dy.contiguous(), dest), None, None
+
+
 def moe_gemm_supported(a, weight):
     """What moe_gemm.hip serves: bf16 on the GPU, E <= 128, M and K
     multiples of 64 (any N, any rows per expert)."""
@@ -353,7 +434,8 @@ def expert_mm(a, weight, offs, impl="torch", row_src=None, dest=None):
     the bits impl="hip" gives on moe_scatter(a, dest, k).  Where
     moe_gemm_supported fails, or under another impl, the rows are scattered
     first and the call goes on as without row_src.  Without row_src
-    "hip-gather" is "hip".
+    "hip-gather" is "hip".  "hip-fused" is "hip-gather" here: its fusion
+    spans both GEMMs and lives in moe_mlp.
 
     Where this build of torch cannot run the grouped GEMM on a's kind of
     device, the helper warns once and from then on loops over the experts'
@@ -377,7 +459,8 @@ def expert_mm(a, weight, offs, impl="torch", row_src=None, dest=None):
             raise ValueError(
                 "expert_mm: with row_src, a is [T, K] with T >= 1 and "
                 "row_src and dest are both [T*k]")
-        if impl == "hip-gather" and moe_gemm_supported(a, weight):
+        if impl in ("hip-gather", "hip-fused") \
+                and moe_gemm_supported(a, weight):
             last_expert_mm_path = "hip-gather"
             return _ExpertMMGatherFn.apply(a.contiguous(),
                                            weight.contiguous(), offs, dest,
@@ -407,14 +490,35 @@ def expert_mm(a, weight, offs, impl="torch", row_src=None, dest=None):
     return _expert_mm_loop(a, weight, offs)
 
 
+def _fused_supported(x, gate_up, down):
+    """What moe_gemm_swiglu.hip serves: moe_gemm_supported for both GEMMs,
+    at least one token, and I a multiple of 64."""
+    return x.shape[0] > 0 and gate_up.shape[1] % 128 == 0 \
+        and moe_gemm_supported(x, gate_up) \
+        and down.shape == (gate_up.shape[0], x.shape[1],
+                           gate_up.shape[1] // 2) \
+        and down.dtype == x.dtype and down.device == x.device
+
+
 def _mlp_chain(x, router_weight, gate_up, down, k, norm, aux, router, index,
                scatter, combine, expert_gemm="torch"):
+    global last_expert_mm_path
     E = gate_up.shape[0]
     logits = F.linear(x, router_weight)
     # without aux the router is called exactly as before the option existed
     idx, w, *losses = router(logits, k, norm, True) if aux \
         else router(logits, k, norm)
     dest, offs = index(idx, E)
+    if expert_gemm == "hip-fused":
+        if _fused_supported(x, gate_up, down):
+            last_expert_mm_path = "hip-fused"
+            w = w.float().contiguous()
+            gu, hw = _GateUpSwigluFn.apply(x.contiguous(),
+                                           gate_up.contiguous(), w, offs, dest)
+            y = _SumFn.apply(_DownSwigluFn.apply(gu, hw, down.contiguous(), w,
+                                                 offs, dest), dest, k)
+            return (y, *losses) if aux else y
+        expert_gemm = "hip-gather"  # the same layer, rounded elsewhere
     if expert_gemm == "hip-gather" and x.shape[0] > 0 \
             and moe_gemm_supported(x, gate_up):
         # gate_up reads x through the row index; h is born sorted, so the
@@ -451,7 +555,12 @@ def moe_mlp(x, router_weight, gate_up, down, k, norm_topk_prob=True,
     the scattered copy of x: the gate_up GEMM and its weight gradient read x
     through moe_row_src's index (moe_gemm_gather.hip), which keeps T*k*H
     bf16 less alive until the backward; outputs and gradients are the same
-    bits."""
+    bits.  "hip-fused" is "hip-gather" with the weighted SwiGLU in the GEMMs'
+    epilogues (moe_gemm_swiglu.hip, I % 64 == 0): the router weight scales h
+    before the down GEMM, the combine sums unweighted and the sorted down
+    output [T*k, H] is not kept for the backward.  The same mathematics with
+    another rounding; on CPU tensors or unsupported shapes it is
+    "hip-gather" with that value's own fallbacks."""
     if expert_gemm not in EXPERT_GEMM_IMPLS:
         raise ValueError(f"moe_mlp: expert_gemm must be one of "
                          f"{EXPERT_GEMM_IMPLS}, got {expert_gemm!r}")

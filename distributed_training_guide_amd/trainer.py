@@ -16,7 +16,9 @@ Extras the reference ships as diff-recipes are first-class flags:
 --fp8-recipe delayed scales by an amax history of --fp8-amax-history),
 --router-aux-loss-coef / --router-z-loss-coef (mixture-of-experts router
 losses, ops/moe.py), --expert-gemm (hand-written grouped expert GEMMs:
-hip, or hip-gather, which also keeps no expert-sorted copy of the tokens).
+hip, hip-gather, which also keeps no expert-sorted copy of the tokens, or
+hip-fused, which also applies the router-weighted SwiGLU in the GEMMs'
+epilogues).
 """
 import argparse
 import dataclasses
@@ -97,14 +99,18 @@ def get_parser(extra: bool = True) -> argparse.ArgumentParser:
                        help="mixture-of-experts models: weight of the "
                             "router z-loss, averaged over the layers")
         p.add_argument("--expert-gemm", default="torch",
-                       choices=["torch", "hip", "hip-gather"],
+                       choices=["torch", "hip", "hip-gather", "hip-fused"],
                        help="mixture-of-experts models: the expert GEMMs as "
                             "torch's grouped GEMM, as the hand-written "
-                            "grouped GEMMs (_hip/moe_gemm.hip), or as those "
+                            "grouped GEMMs (_hip/moe_gemm.hip), as those "
                             "with the gate_up GEMM reading the tokens through "
                             "a row index, so that no expert-sorted copy of "
                             "them is made or kept for the backward "
-                            "(_hip/moe_gemm_gather.hip)")
+                            "(_hip/moe_gemm_gather.hip), or as those with "
+                            "the router-weighted SwiGLU in the GEMMs' "
+                            "epilogues as well, so that the sorted down "
+                            "output is not kept either "
+                            "(_hip/moe_gemm_swiglu.hip)")
         p.add_argument("--deterministic", action="store_true")
         p.add_argument("--wandb", action="store_true")
         p.add_argument("--wandb-mode", default="rank0",

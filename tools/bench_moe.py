@@ -45,6 +45,13 @@ of moe_gemm_gather.hip against scatter + forward, the gate_up dW both ways,
 the row index build, the whole layer forward + backward, and the memory a
 layer holds after its forward and at its peak.
 
+--fused times expert_gemm="hip-fused" against "hip-gather" instead (default
+--out profiles/moe_gemm_swiglu.json), alternating in one run: the gate_up
+forward with the SwiGLU epilogue against gather forward + silu_mul, the down
+dA with the SwiGLU-backward epilogue + the unweighted scatter against dA +
+silu_mul backward + the combine's backward, the whole layer forward +
+backward, and the memory a layer holds after its forward and at its peak.
+
 --e2e-layers L additionally times training steps of a cut-down model of the
 same layer shape with L layers (the 30B model's 366 GB of parameter and
 optimizer state do not fit one GPU).  Results go to --out; no threshold is
@@ -225,16 +232,28 @@ def gather_mode(args, C, moe, x, router_w, gate_up, down, dest, offs, dy, fwd,
         "hip_dw": lambda: C.moe_gemm_dw(g, xp, offs),
         "gather_dw": lambda: C.moe_gemm_dw_gather(g, x, row_src, offs),
     }
-    for impl in ("hip", "hip-gather"):
-        variants[f"{impl}_layer_fwd"] = fwd(
-            impl, lambda *a, impl=impl: moe.moe_mlp(*a, k, True,
-                                                    expert_gemm=impl),
-            x, router_w, gate_up, down)
-        variants[f"{impl}_layer_bwd"] = bwd(impl, dy)
+    impls = ("hip", "hip-gather")
+    variants.update(layer_variants(args, moe, impls, x, router_w, gate_up,
+                                   down, dy, fwd, bwd))
     res = timed(variants, args.warmup, args.repeats)
     res.update(same)
     del xp, g
-    for impl in ("hip", "hip-gather"):
+    layer_memory(res, impls, variants)
+    return res
+
+
+def layer_variants(args, moe, impls, x, router_w, gate_up, down, dy, fwd, bwd):
+    return {f"{impl}_layer_{d}": v for impl in impls for d, v in (
+        ("fwd", fwd(impl, lambda *a, impl=impl: moe.moe_mlp(
+            *a, args.top_k, True, expert_gemm=impl), x, router_w, gate_up,
+            down)),
+        ("bwd", bwd(impl, dy)))}
+
+
+def layer_memory(res, impls, variants):
+    """fwd+bwd sums, and a layer step's held and peak allocation above what
+    is allocated before it"""
+    for impl in impls:
         res[f"{impl}_layer_fwdbwd_ms"] = round(
             res[f"{impl}_layer_fwd_ms"] + res[f"{impl}_layer_bwd_ms"], 4)
         torch.cuda.synchronize()
@@ -248,6 +267,45 @@ def gather_mode(args, C, moe, x, router_w, gate_up, down, dest, offs, dy, fwd,
         res[f"{impl}_layer_held_after_fwd_mb"] = round(held / 1e6, 1)
         res[f"{impl}_layer_peak_mb"] = round(
             (torch.cuda.max_memory_allocated() - base) / 1e6, 1)
+
+
+def fused_mode(args, C, moe, x, router_w, gate_up, down, dest, offs, w, dy,
+               fwd, bwd):
+    """expert_gemm="hip-fused" against "hip-gather", alternating in one run:
+    the two epilogue-fused kernels of moe_gemm_swiglu.hip against the kernels
+    they replace, the whole layer, and its memory."""
+    k = args.top_k
+    N = dest.numel()
+    row_src, w_row = C.moe_row_src(dest, k), C.moe_row_w(dest, w)
+    gu, hw = C.moe_gemm_gu_swiglu(x, row_src, w_row, gate_up, offs)
+    yp = C.moe_gemm_rows(hw, down, offs, False)
+    dyp = torch.randn(N, x.shape[1], device=x.device, dtype=x.dtype)
+    res = {"gu_equal": torch.equal(
+        gu, C.moe_gemm_rows_gather(x, row_src, gate_up, offs))}
+
+    def gather_bwd():
+        dyp_, _ = C.moe_combine_bwd(dy, dest, w, yp)
+        return C.silu_mul_bwd(C.moe_gemm_rows(dyp_, down, offs, True), gu)
+
+    variants = {
+        "row_w": (lambda: C.moe_row_w(dest, w), SMALL_OP_LAUNCHES),
+        "gather_fwd_silu": lambda: C.silu_mul_fwd(
+            C.moe_gemm_rows_gather(x, row_src, gate_up, offs)),
+        "fused_fwd": lambda: C.moe_gemm_gu_swiglu(x, row_src, w_row, gate_up,
+                                                  offs),
+        "gather_combine_bwd_da_silu_bwd": gather_bwd,
+        "fused_scatter_da": lambda: C.moe_gemm_da_swiglu(
+            C.moe_scatter(dy, dest), down, gu, w_row, offs, dest),
+        "hip_da": lambda: C.moe_gemm_rows(dyp, down, offs, True),
+        "fused_da": lambda: C.moe_gemm_da_swiglu(dyp, down, gu, w_row, offs,
+                                                 dest),
+    }
+    impls = ("hip-gather", "hip-fused")
+    variants.update(layer_variants(args, moe, impls, x, router_w, gate_up,
+                                   down, dy, fwd, bwd))
+    res.update(timed(variants, args.warmup, args.repeats))
+    del gu, hw, yp, dyp
+    layer_memory(res, impls, variants)
     return res
 
 
@@ -270,12 +328,16 @@ def main():
     p.add_argument("--gather", action="store_true",
                    help="time expert_gemm='hip-gather' "
                         "(_hip/moe_gemm_gather.hip) against 'hip'")
+    p.add_argument("--fused", action="store_true",
+                   help="time expert_gemm='hip-fused' "
+                        "(_hip/moe_gemm_swiglu.hip) against 'hip-gather'")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.out is None:
         args.out = "profiles/moe_aux.json" if args.aux else \
             "profiles/moe_gemm.json" if args.expert_gemm else \
             "profiles/moe_gemm_gather.json" if args.gather else \
+            "profiles/moe_gemm_swiglu.json" if args.fused else \
             "profiles/moe.json"
 
     if not torch.cuda.is_available():
@@ -406,6 +468,15 @@ def main():
         out = Path(args.out)
         out.parent.mkdir(parents=True, exist_ok=True)
         out.write_text(json.dumps({"gather": result}, indent=2) + "\n")
+        return
+    if args.fused:
+        del yp, dxp, dyp, xp
+        result.update(fused_mode(args, C, moe, x, router_w, gate_up, down,
+                                 dest, offs, w, dy, fwd, bwd))
+        print(json.dumps(result))
+        out = Path(args.out)
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps({"fused": result}, indent=2) + "\n")
         return
     result.update(timed(variants, args.warmup, args.repeats))
     result["expert_gemm_path"] = moe.last_expert_mm_path

@@ -75,14 +75,15 @@ def _needs_build(src: Path, obj: Path, extra_deps=()):
 # determinism recipe relies on, so the precaution applies in full; the
 # kernels wait on memory, not on the VALU; moe_gemm.hip is new and follows
 # the rule: its f32 arithmetic is MFMA, the flag touches nothing in its
-# loops; moe_gemm_gather.hip shares that tile code and its flags).  The
+# loops; moe_gemm_gather.hip and moe_gemm_swiglu.hip share that tile code and
+# its flags).  The
 # older files keep the flags
 # their committed resource tables and bit-for-bit output dumps were made with.
 # The entry can go once the toolchain or the hardware note is retired.
 _NO_PACKED_F32 = {"moe_router.hip", "moe_router_aux.hip",
                   "moe_dispatch.hip", "fp8_delayed.hip",
                   "embedding_bwd_sorted.hip", "moe_gemm.hip",
-                  "moe_gemm_gather.hip"}
+                  "moe_gemm_gather.hip", "moe_gemm_swiglu.hip"}
 _NO_PACKED_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang",
                         "-packed-fp32-ops"]
 
